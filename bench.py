@@ -4,7 +4,9 @@ One "step" = one pass of the hot path (MPCWholeBody.solve for every instance of 
 controllers/mpc_wholebody_qref.py:287-331) over a fixed synthetic batch whose inputs are already
 resident in HBM.  N ranks: the global batch is sharded contiguously over ranks (no data-path
 collective), followed by the one all-gather of the solved trajectories the metric's config names.
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times `--steps` steps and prints the headline; `--full` adds
+the extras (other modes, sizes and configs, the CPU baseline) to the same line; `--dump-outputs DIR` writes what the last
+timed step computed.
 """
 import argparse
 import contextlib
@@ -56,6 +58,27 @@ def algorithmic_bytes_per_solve(N, nx, nu, M):
     return 8 * (nx + nx * (N + 1) + nu * N + nu * N + 3 * M) + 8 * (nx * (N + 1) + nu * N + (N + 1))
 
 
+DUMP_NAMES = ("X", "U", "s", "status", "iters", "cost", "err")
+DUMP_MAX_BYTES = 64 * 1000 * 1000
+
+
+def dump_outputs(path, out):
+    """Writes the output set of the last timed step (what solve_batch_device returns to its caller) as path/<name>.npy in
+    float64.  A batch whose outputs exceed 64 MB is written as a fixed, seeded sample of instances (rows listed in
+    instance_index.npy), so that two builds given the same arguments write the same rows."""
+    os.makedirs(path, exist_ok=True)
+    B = out["X"].shape[0]
+    per_instance = sum(8 * out[k][0].numel() for k in DUMP_NAMES) if B else 0
+    rows = None
+    if B * per_instance > DUMP_MAX_BYTES:
+        n = (DUMP_MAX_BYTES - 64 * 1024) // (per_instance + 8)
+        rows = np.sort(np.random.default_rng(0).choice(B, size=n, replace=False))
+        np.save(os.path.join(path, "instance_index.npy"), rows.astype(np.float64))
+    for k in DUMP_NAMES:
+        a = out[k].detach().cpu().numpy().astype(np.float64)
+        np.save(os.path.join(path, k + ".npy"), a if rows is None else a[rows])
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -86,8 +109,18 @@ def main():
                     help="c4: BASELINE metric (default). c5: N=30, 8 moving obstacles, warm-started receding horizon (1 GPU)")
     ap.add_argument("--ticks", type=int, default=10)
     ap.add_argument("--async-budget", type=int, default=192, help="--config c5: iterations per launch of the asynchronous receding-horizon extra")
+    ap.add_argument("--full", action="store_true",
+                    help="c4: beyond the headline, also run the extras (collective and rank-0) and the CPU baseline; "
+                         "a plain run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="c4: write what the last timed step computed (X, U, s, status, iters, cost, err of this rank's batch) "
+                         "as DIR/<name>.npy in float64")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1, --warmup >= 0")
     if args.config == "c5":
+        if args.dump_outputs:
+            raise SystemExit("--dump-outputs is implemented for --config c4 only")
         return main_c5(args)
     if args.budget < 0 or args.pipelined_budget < 1:
         raise SystemExit("--budget must be >= 0, --pipelined-budget >= 1")
@@ -304,7 +337,10 @@ def main():
         del P
         return r_
 
-    if not args.no_extras and world > 1:
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, out)
+
+    if args.full and not args.no_extras and world > 1:
         if budget == 0:
             extras["pipelined_budget"] = pipelined_extra()
         if world > 1 and args.scaling == "weak":
@@ -386,7 +422,7 @@ def main():
         if world > 1:
             res["gather_checked"] = R["gather_ok"]        # every rank found its own records, bit for bit, in the gathered table
         ev0, ev1 = evs[0]
-        if world == 1 and not args.no_cpu and not args.no_extras:   # (--no-cpu = the profiler passes: they see the warm-up and timed launches only)
+        if world == 1 and args.full and not args.no_cpu and not args.no_extras:   # (--no-cpu = the profiler passes: they see the warm-up and timed launches only)
             # Extras, outside the timed region.
             # (0) config C5 (N = 30, 8 moving obstacles, warm-started receding horizon) in short form: `python bench.py --config c5`
             # prints the full line.  FIRST among the extras: its groups run on their own HIP streams, and streams are mapped to the
@@ -534,27 +570,28 @@ def main():
                     res["pipelined_budget"] = pipelined_extra()
                 except Exception as e:
                     res["pipelined_budget"] = {"error": repr(e)}
-        if world == 1 and not args.no_cpu:
+        if world == 1 and args.full and not args.no_cpu:
             res["cpu_baseline"] = cpu_baseline(d, N, M, min(args.cpu_sample, Bl), out["X"])
         # one word per extra and the figures the documents quote, flat, where a reader of the line's tail finds them
-        names = ("c5", "schedule_hint", "continuation", "generic_kernel", "c1_shape_generic_kernel", "two_streams", "host_pointer_api",
-                 "single_solve_latency_ms", "large_batch", "stream_of_batches", "pipelined_budget", "strong_scaling", "cpu_baseline")
-        res["extras_status"] = {k: ("error" if isinstance(res[k], dict) and "error" in res[k] else "ok") for k in names if k in res}
-        g = lambda *path: _dig(res, path)
-        res["extras_summary"] = {k: v for k, v in {
-            "generic_kernel_c4_solves_s": g("generic_kernel", "value"),
-            "c1_as_written_solves_s": g("c1_shape_generic_kernel", "rows_as_written", "value"),
-            "c1_as_written_converged_frac": g("c1_shape_generic_kernel", "rows_as_written", "converged_frac"),
-            "c5_lock_step_solves_s": g("c5", "value"),
-            "c5_best_groups_solves_s": g("c5", "groups_out_of_phase", "best", "value"),
-            "c5_converged_frac": g("c5", "converged_frac"),
-            "hinted_ms": g("schedule_hint", "hinted_ms"),
-            "batch_order_ms": g("schedule_hint", "batch_order_ms"),
-            "two_streams_solves_s": g("two_streams", "value"),
-            "stream_of_batches_plain_ms": g("stream_of_batches", "plain", "ms_per_batch"),
-            "single_solve_latency_ms": g("single_solve_latency_ms", "median"),
-            "cpu_port_solves_s": g("cpu_baseline", "value"),
-        }.items() if v is not None}
+        if args.full:
+            names = ("c5", "schedule_hint", "continuation", "generic_kernel", "c1_shape_generic_kernel", "two_streams", "host_pointer_api",
+                     "single_solve_latency_ms", "large_batch", "stream_of_batches", "pipelined_budget", "strong_scaling", "cpu_baseline")
+            g = lambda *path: _dig(res, path)
+            res["extras_status"] = {k: ("error" if isinstance(res[k], dict) and "error" in res[k] else "ok") for k in names if k in res}
+            res["extras_summary"] = {k: v for k, v in {
+                "generic_kernel_c4_solves_s": g("generic_kernel", "value"),
+                "c1_as_written_solves_s": g("c1_shape_generic_kernel", "rows_as_written", "value"),
+                "c1_as_written_converged_frac": g("c1_shape_generic_kernel", "rows_as_written", "converged_frac"),
+                "c5_lock_step_solves_s": g("c5", "value"),
+                "c5_best_groups_solves_s": g("c5", "groups_out_of_phase", "best", "value"),
+                "c5_converged_frac": g("c5", "converged_frac"),
+                "hinted_ms": g("schedule_hint", "hinted_ms"),
+                "batch_order_ms": g("schedule_hint", "batch_order_ms"),
+                "two_streams_solves_s": g("two_streams", "value"),
+                "stream_of_batches_plain_ms": g("stream_of_batches", "plain", "ms_per_batch"),
+                "single_solve_latency_ms": g("single_solve_latency_ms", "median"),
+                "cpu_port_solves_s": g("cpu_baseline", "value"),
+            }.items() if v is not None}
         print(json.dumps(res))
     if world > 1:
         dist.destroy_process_group()

@@ -33,7 +33,7 @@ python3 tools/probe_base.py > $o/base_c2.txt 2>&1 || true
 cp $o/pmc_traffic.json profiles/${tag}_pmc_traffic.json; cp $o/pmc_mfma.json profiles/${tag}_pmc_mfma.json
 cp $o/c5_pmc_traffic.json profiles/${tag}_c5_pmc_traffic.json
 echo "[7/8] bench lines"
-python3 bench.py --steps 20 --warmup 3 > $o/bench.json 2> $o/bench.err
+python3 bench.py --full --steps 20 --warmup 3 > $o/bench.json 2> $o/bench.err
 echo "[8/8] C5 bench line"
 python3 bench.py --config c5 --steps 2 --warmup 2 > $o/bench_c5.json 2> $o/bench_c5.err
 tail -c 600 $o/bench.json

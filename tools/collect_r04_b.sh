@@ -16,6 +16,6 @@ cp $o/c5_pmc_traffic.json profiles/${tag}_c5_pmc_traffic.json
 echo "[7] C5 phase stamps"
 MMPC_STAMP_LIB=$PWD/mobile-manipulator-mpc_amd/csrc/libmmpc_stampc5.so MMPC_PROBE_N=30 MMPC_PROBE_M=8 MMPC_PROBE_DISTINCT=1 python3 tools/probe_stamps.py 2>&1 | grep -v amdgpu.ids > $o/c5_phase_stamps.txt || true
 echo "[8] bench lines"
-python3 bench.py --steps 20 --warmup 3 > $o/bench.json 2> $o/bench.err
+python3 bench.py --full --steps 20 --warmup 3 > $o/bench.json 2> $o/bench.err
 python3 bench.py --config c5 --steps 2 --warmup 2 > $o/bench_c5.json 2> $o/bench_c5.err
 tail -c 900 $o/bench.json; echo; tail -c 500 $o/bench_c5.json

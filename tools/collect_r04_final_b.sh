@@ -20,6 +20,6 @@ for s in 3 4 5 6 7 8 9 10 11 12; do python3 tools/probe_order.py $s 2>&1 | grep 
 timeout -k 10 400 python3 tools/c5_seed_sweep.py 2>&1 | grep -v amdgpu.ids > $o/c5_seed_sweep.txt; cat $o/c5_seed_sweep.txt
 timeout -k 10 400 python3 tools/seed_sweep.py --no-oracle $(seq 3 80) 2>&1 | grep -v amdgpu.ids > $o/seed_sweep.txt; tail -3 $o/seed_sweep.txt
 echo "[9] bench lines"
-python3 bench.py --steps 20 --warmup 3 > $o/bench.json 2> $o/bench.err
+python3 bench.py --full --steps 20 --warmup 3 > $o/bench.json 2> $o/bench.err
 python3 bench.py --config c5 --steps 2 --warmup 2 > $o/bench_c5.json 2> $o/bench_c5.err
 tail -c 900 $o/bench.json; echo; tail -c 500 $o/bench_c5.json
