@@ -48,8 +48,16 @@ extern "C" {
  * (mpc_base.py:7-17).  +-INFINITY marks an absent bound (the reference uses ca.inf). */
 typedef struct mmpc_config {
     int kind;          /* MMPC_KIND_* */
-    int N;             /* horizon, 1 <= N <= 63 */
-    int M;             /* circle obstacles per instance, 0 <= M <= 16 (len(obstacle_list)) */
+    int N;             /* horizon, 1 <= N <= 63, and the LDS slab of the generic kernel must fit (see below) */
+    int M;             /* circle obstacles per instance, 0 <= M <= 16 (len(obstacle_list)).
+                          Envelope: mmpc_create accepts a config when, besides these ranges, the generic kernel's LDS slab for it
+                          (mmpc_lds_bytes of a handle that runs the generic kernel) is at most 160 KiB; otherwise it returns
+                          MMPC_E_ARG with an error that names LDS.  Largest N at M = 0 / 5 / 8 / 16:
+                            whole-body         49 / 44 / 41 / 35    (obs_per_stage: 49 / 42 / 39 / 32)
+                            base               63 / 63 / 63 / 59    (obs_per_stage: 63 / 63 / 63 / 51; N = 63 up to M = 13, 10)
+                            pose-reference     55 / 49 / 45 / 38    (obs_per_stage: 55 / 47 / 43 / 35)
+                          Half-space planes at N = 20: intended rows fit for L <= 8 at any M; as written, L = 5 fits up to
+                          M = 10, L = 6 up to M = 3, L = 7 and 8 never; at N = 30, as-written L = 2 fits with M = 0 only. */
     int obs_per_stage; /* 0: obs[B][M][3]; 1: obs[B][N+1][M][3] */
     int max_batch;     /* capacity of the device-side buffers: warm start, outputs of the host-pointer call, launch order and - for
                           horizons N >= 21 on a specialised kernel - one 8 (N nu (nx + 1) + N nu (nu - 1) / 2 + 64) byte block of

@@ -133,8 +133,10 @@ extern "C" int mmpc_emu_solve(int kind, const MmpcParams *P, int B, const double
     else run<2>(P, B, x_init, traj_ref, u_ref, u_last, x_guess, obs, X, U, s, status, iters, cost, err, reverse);
     return 0;
 }
-extern "C" int mmpc_emu_lds_doubles(int kind, int N, int M, int obs_per_stage) {
-    return kind == 0 ? mmpc_layout<0>(N, M, obs_per_stage).total : kind == 1 ? mmpc_layout<1>(N, M, obs_per_stage).total : mmpc_layout<2>(N, M, obs_per_stage).total;
+// LDS slab of the generic kernel as mmpc_create sizes it: nhs = half-space rows per stage (6 when L > 0), nq = as-written extra
+// rows per stage (6 (L - 1)); both whole-body kind only
+extern "C" int mmpc_emu_lds_doubles(int kind, int N, int M, int obs_per_stage, int nhs, int nq) {
+    return kind == 0 ? mmpc_layout<0>(N, M, obs_per_stage, nhs, nq).total : kind == 1 ? mmpc_layout<1>(N, M, obs_per_stage).total : mmpc_layout<2>(N, M, obs_per_stage).total;
 }
 extern "C" int mmpc_emu_params_size() { return (int)sizeof(MmpcParams); }
 

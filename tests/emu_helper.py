@@ -97,6 +97,30 @@ def solve_batch(par, x_init, traj_ref, u_ref, u_last, obs, x_guess=None, reverse
     return dict(X=X, U=U, s=s, status=status, iters=iters, cost=cost, err=err)
 
 
+def lds_bytes(kind, N, M, obs_per_stage=False, L=0, as_written=False):
+    """Bytes of LDS the generic kernel's slab takes for this config, from the kernel's own layout (mmpc_layout) on the host:
+    kind 0 whole-body, 1 base, 2 pose-reference; L half-space planes (whole-body only), as_written their extra rows (L >= 2)."""
+    lib = C.CDLL(build())
+    nhs = 6 if kind == 0 and L > 0 else 0
+    nq = 6 * (L - 1) if kind == 0 and L >= 2 and as_written else 0
+    return 8 * lib.mmpc_emu_lds_doubles(int(kind), int(N), int(M), int(bool(obs_per_stage)), nhs, nq)
+
+
+def pose_batch(B, N, seed=5):
+    """Seeded inputs of the pose-reference kind: x_init (B,9), endpoint-pose reference (B,N+1,4) on a straight line from the
+    start pose, two obstacles (B,2,3) - one beside the line half way, one far off."""
+    from oracle import nlp
+    rng = np.random.default_rng(seed)
+    x0 = np.zeros((B, 9)); ref = np.zeros((B, N + 1, 4)); obs = np.zeros((B, 2, 3))
+    for b in range(B):
+        x0[b] = [0, 0, rng.uniform(-1, 1), rng.uniform(0, 0.5), 0, 0, rng.uniform(-0.5, 0.5), rng.uniform(-2, -0.3), rng.uniform(0.3, 2.5)]
+        E0 = nlp.endpoint_pose(x0[b])
+        tgt = E0 + np.array([rng.uniform(0.5, 2), rng.uniform(-1, 1), rng.uniform(-0.2, 0.2), rng.uniform(-0.5, 0.5)])
+        ref[b] = np.linspace(E0, tgt, N + 1)
+        obs[b] = [[E0[0] + 0.5 * (tgt[0] - E0[0]), E0[1] + 0.5 * (tgt[1] - E0[1]) + 0.3, 0.3], [3, 3, 0.2]]
+    return x0, ref, obs
+
+
 def ik_batch(q0, target_xz, asan=False):
     """mmpc_ik_solve (the function the GPU kernel runs per lane) on the host."""
     lib = C.CDLL(build(asan))

@@ -131,12 +131,73 @@ def test_emu_hard_instances_converge():
 
 
 def test_emu_edge_sizes():
-    """M=0 (no obstacles), N=1, and N=63 (largest supported horizon: 64 stages = one per lane)."""
+    """M=0 (no obstacles), N=1, and N=63 (the largest horizon of the stage-per-lane layout: 64 stages = one per lane; the GPU
+    refuses whole-body N = 63, whose LDS slab exceeds 160 KiB - tests/test_gpu_envelope.py)."""
     for N, M in ((1, 0), (3, 1), (63, 2)):
         B = 2
         d = synth.make_batch(B, N=N, M=max(M, 1), config_id=7)
         obs = d["obs"][:, :M]
         _cmp(nlp.WholeBodyParams(N=N), d, obs, np.zeros((B, N, 5)))
+
+
+def test_lds_envelope_table_of_the_header():
+    """The largest horizons include/mmpc.h (mmpc_config) and DESIGN section 4 document are those the kernel's own slab layout
+    gives (tests/test_gpu_envelope.py: mmpc_create accepts exactly those)."""
+    table = {(0, False): (49, 44, 41, 35), (0, True): (49, 42, 39, 32), (1, False): (63, 63, 63, 59), (1, True): (63, 63, 63, 51),
+             (2, False): (55, 49, 45, 38), (2, True): (55, 47, 43, 35)}
+    fits = lambda *a, **k: emu_helper.lds_bytes(*a, **k) <= 160 * 1024
+    for (kind, ops), n_max in table.items():
+        assert tuple(max(N for N in range(1, 64) if fits(kind, N, M, ops)) for M in (0, 5, 8, 16)) == n_max, (kind, ops)
+    assert max(M for M in range(17) if fits(1, 63, M, False)) == 13 and max(M for M in range(17) if fits(1, 63, M, True)) == 10
+    assert all(fits(0, 20, M, ops, L=8) for M in range(17) for ops in (False, True))
+    assert [max([M for M in range(17) if fits(0, 20, M, False, L, True)], default=-1) for L in (5, 6, 7, 8)] == [10, 3, -1, -1]
+    assert [M for M in range(17) if fits(0, 30, M, False, 2, True)] == [0]
+    assert not any(fits(0, 63, M, False) for M in range(17))          # whole-body N = 63 is refused at every M
+
+
+@pytest.mark.parametrize("spec", [("wb", 49, 0, False), ("wb", 35, 16, False), ("wb", 32, 16, True), ("base", 63, 13, False),
+                                  ("pose", 55, 0, False)], ids=["wb-N49-M0", "wb-N35-M16", "wb-N32-M16-ops", "base-N63-M13", "pose-N55-M0"])
+def test_emu_edge_sizes_at_the_lds_limit(spec):
+    """The largest shapes mmpc_create accepts (their slab is within a few KB of 160 KiB): the emulated generic kernel against
+    the oracle, so that a logic error at the edge of the envelope shows on a CPU run (tests/test_gpu_envelope.py: the GPU)."""
+    kind, N, M, ops = spec
+    B = 2
+    assert 150 * 1024 < emu_helper.lds_bytes({"wb": 0, "base": 1, "pose": 2}[kind], N, M, ops) <= 160 * 1024
+    if kind == "pose":
+        par = nlp.pose_ref_params(N=N)
+        x, ref, obs = emu_helper.pose_batch(B, N, seed=N)
+        d = dict(x_init=x, traj_ref=ref, u_ref=np.zeros((B, N, 5)))
+        obs = obs[:, :M]
+    else:
+        par = nlp.WholeBodyParams(N=N) if kind == "wb" else nlp.BaseParams(N=N)
+        d = synth.make_batch(B, N=N, M=M, kind="wholebody" if kind == "wb" else "base", config_id=7, moving=ops)
+        d["x_init"] = np.clip(d["x_init"], par.xlim[0], par.xlim[1]) if kind == "wb" else d["x_init"]
+        obs = d["obs"]
+        if ops:
+            obs = np.repeat(obs[:, None], N + 1, axis=1)
+            obs[..., :2] += d["obs_vel"][:, None] * (par.dt * np.arange(N + 1))[None, :, None, None]
+    _cmp(par, d, obs, np.zeros((B, N, par.nu)))
+
+
+@pytest.mark.parametrize("M,L,aw", [(16, 8, False), (3, 6, True)], ids=["M16-L8", "M3-L6-aw"])
+def test_emu_halfspace_planes_at_the_lds_limit(M, L, aw):
+    """N = 20 with eight intended half-space planes and sixteen discs, and with six planes as written (the most that fit): the
+    starts around the demo's planes (synth.make_c1_starts), the planes beyond its three as jittered copies."""
+    B, N = 2, 20
+    x, tr, obs, hs0 = synth.make_c1_starts(B, N=N, nplanes=3, seed=L)
+    rng = np.random.default_rng(L)
+    hs = np.array([hs0[i % 3] + (np.r_[rng.uniform(-0.2, 0.2, 3), rng.uniform(-0.15, 0.15, 3)] if i >= 3 else 0) for i in range(L)])
+    hs[:, 3:] /= np.linalg.norm(hs[:, 3:], axis=1, keepdims=True)
+    far = np.stack([[[x[b, 0] + 2.0 + 0.3 * m, x[b, 1] + (-1) ** m * (1.0 + 0.1 * m), 0.2] for m in range(M)] for b in range(B)])
+    obs = np.concatenate([obs, far], 1)[:, :M]
+    par = nlp.WholeBodyParams(N=N)
+    z = np.zeros((B, N, 5))
+    assert emu_helper.lds_bytes(0, N, M, False, L, aw) <= 160 * 1024
+    o = coracle.solve_batch(par, x, tr, z, z, obs, hs=hs, as_written=aw, max_iter=2000)
+    e = emu_helper.solve_batch(par, x, tr, z, z, obs, hs=hs, as_written=aw, max_iter=2000)
+    assert (o["status"] == 0).all() and (e["status"] == 0).all()
+    assert np.array_equal(o["iters"], e["iters"]), (o["iters"], e["iters"])
+    assert np.abs(o["X"] - e["X"]).max() < 1e-6 and np.abs(o["U"] - e["U"]).max() < 1e-6
 
 
 def test_emu_under_asan():
@@ -164,24 +225,12 @@ def test_emu_under_asan():
     assert p.returncode == 0 and "ASAN-OK" in p.stdout, p.stderr[-3000:]
 
 
-def _pose_batch(B, N, seed=5):
-    rng = np.random.default_rng(seed)
-    x0 = np.zeros((B, 9)); ref = np.zeros((B, N + 1, 4)); obs = np.zeros((B, 2, 3))
-    for b in range(B):
-        x0[b] = [0, 0, rng.uniform(-1, 1), rng.uniform(0, 0.5), 0, 0, rng.uniform(-0.5, 0.5), rng.uniform(-2, -0.3), rng.uniform(0.3, 2.5)]
-        E0 = nlp.endpoint_pose(x0[b])
-        tgt = E0 + np.array([rng.uniform(0.5, 2), rng.uniform(-1, 1), rng.uniform(-0.2, 0.2), rng.uniform(-0.5, 0.5)])
-        ref[b] = np.linspace(E0, tgt, N + 1)
-        obs[b] = [[E0[0] + 0.5 * (tgt[0] - E0[0]), E0[1] + 0.5 * (tgt[1] - E0[1]) + 0.3, 0.3], [3, 3, 0.2]]
-    return x0, ref, obs
-
-
 def test_emu_pose_reference_controller():
     """controllers/mpc_wholebody.py (endpoint-pose reference, KIND 2 of the generic kernel) vs the C and numpy oracles,
     first solve and a warm-started second one (X and U initial guesses = previous optimum, :134-139)."""
     N, B = 10, 6
     par = nlp.pose_ref_params(N=N)
-    x0, ref, obs = _pose_batch(B, N)
+    x0, ref, obs = emu_helper.pose_batch(B, N)
     ul = np.zeros((B, N, 5)); ur = np.zeros((B, N, 5))
     o = coracle.solve_batch(par, x0, ref, ur, ul, obs)
     e = emu_helper.solve_batch(par, x0, ref, ur, ul, obs)
