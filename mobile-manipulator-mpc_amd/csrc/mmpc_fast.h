@@ -391,11 +391,16 @@ static inline double mmpc_emu_red4(double (*wr)[9], int i, int op) {
 // compile-time switch handed to the generic lambdas of the assembly / row-step phases (corrected pass of the second-order correction or not)
 template <bool B> struct MmpcTag { static constexpr bool value = B; };
 
-// product accumulator for sum(log t): the slacks themselves are multiplied and ONE logarithm is taken per lane and phase.  A lane
-// multiplies at most ten box slacks (>= 1e-15 by mmpc_box_t) or nine row slacks between init() and value(): the product stays a normal
-// number down to slacks of 1e-30, and scaling by powers of two being exact it has the mantissa the product of the mantissas had
-// (rounds 1-3 split every factor with frexp: four instructions per row instead of one).  `ex` carries the exponent handed over
-// between the two evaluation phases of the long horizons.
+// product accumulator for sum(log t): the slacks themselves are multiplied and ONE logarithm is taken per lane and phase (rounds 1-3
+// split every factor with frexp: four instructions per row instead of one).  Nothing rescales the product on the way, so the number of
+// factors a lane multiplies between init() and value() is what keeps it a normal number.  The three accumulation sites of
+// mmpc_fast_iter.inc multiply, per lane: 2 NPASS box slacks (N = 20: 10, N = 30: 14, base N = 15: 4; an absent side is the factor 1),
+// each in [1e-15 (mmpc_box_t), 2 x 1e19 (mmpc_bound_active)]; or the circle rows of the lane - handed from the row lanes to the stage
+// lane as (mant, ex) where RG > 1 - and the NSELF self-collision rows of its stage (5 + 4 = 9, 4 + 4, 3 + 4, 1 + 0), whose slacks
+// have no floor: nine of them leave the normal range only below 1e-34 each.  mmpc_solve_fast asserts these counts per instantiation
+// (19 decimal digits per factor upwards, 15 downwards for the box slacks); tests/test_primitives_cpu.py and test_gpu_primitives.py run
+// 1 .. 14 factors at both ends of the range.  The accuracy: k roundings of the product, the series, the final sum: <= (k + 2) 2^-53 +
+// 2 x 2^-53 |value| (same tests).  `ex` carries the exponent handed over between the two evaluation phases of the long horizons.
 struct MmpcLogAcc {
     double mant; int ex;
     MMPC_DEV void init() { mant = 1.0; ex = 0; }
@@ -416,6 +421,12 @@ MMPC_DEV void mmpc_solve_fast(const MmpcParams &P, const MmpcIO io, double *lds 
     constexpr int NPASS = F::NPASS, NPAIR = F::NPAIR, NKB = F::NKB, NPU = F::NPU;
     constexpr int M = MC;   // number of circle obstacles is a template parameter on this path
     constexpr int RG = F::RG, MCR = MmpcLaneState<KIND, N, MC>::MCR;   // circle rows: RG lanes per stage, MCR rows per lane
+    // MmpcLogAcc multiplies its factors without rescaling: the largest number of factors one lane multiplies between init() and value()
+    // in this instantiation (E1 of mmpc_fast_iter.inc: row lanes + stage lanes form one chain, the pair lanes another) must keep
+    // the product inside the normal range - box slacks lie in [1e-15, 2e19], a row slack is a distance: below 1e19 like every bound
+    constexpr int LOGF_BOX = 2 * NPASS, LOGF_ROW = (RG > 1 ? MCR : M) + NSELF, LOGF = LOGF_BOX > LOGF_ROW ? LOGF_BOX : LOGF_ROW;
+    static_assert(19 * LOGF < 300, "MmpcLogAcc: the product of this many slacks of 1e19 can overflow");
+    static_assert(15 * LOGF_BOX < 300, "MmpcLogAcc: the product of this many box slacks of 1e-15 can leave the normal range");
 // lane -> (row group rs, stage rk) of the circle rows; row slot r of the lane is obstacle rs + RG r
 #define MMPC_ROW_LANE const int rs = RG > 1 ? lane / NS : 0, rk = lane - rs * NS; const bool rlane = M > 0 && lane < RG * NS;
     // stages per trip of the Riccati / forward loops: unrolling saves the per-stage pointer bumps and register shuffles,

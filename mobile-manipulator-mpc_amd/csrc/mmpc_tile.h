@@ -33,13 +33,20 @@ MMPC_DEV double mmpc_rcp(double x) { return 1.0 / x; }
 MMPC_DEV double mmpc_rsqrt(double x) { return 1.0 / sqrt(x); }
 MMPC_DEV double mmpc_rcp3(double x) { return 1.0 / x; }
 MMPC_DEV double mmpc_rcp_piv(double x) { return 1.0 / x; }
-MMPC_DEV double mmpc_powf(double x, float e) { return (double)exp2f(e * log2f((float)x)); }
+MMPC_DEV float mmpc_log2f_raw(float x) { return log2f(x); }
+MMPC_DEV float mmpc_exp2f_raw(float x) { return exp2f(x); }
 MMPC_DEV void mmpc_sched_fence() {}
 #else
-// v_rcp_f64 / v_rsq_f64 (seeds good to 2^-24, tools/rcp_probe.hip) + one cubic step: 1.1e-16 / 1.4e-16 worst relative error in three
-// / five dependent operations; the IEEE division / sqrt sequences are ~3x longer
+// v_rcp_f64 / v_rsq_f64 + one cubic step, in three / five dependent operations; the IEEE division / sqrt sequences are ~3x longer.
+// Worst relative error, exact rational arithmetic over [1e-30, 1e30] and the mantissa edges (tests/test_gpu_primitives.py, MI355X):
+//   mmpc_rcp, mmpc_rcp3   derived bound 2^-53 (1 + 2^-7) = 1.119e-16 (the final fma's rounding; e^3 is below 2^-60)   measured 1.110e-16
+//   mmpc_rsqrt            derived bound 1.5 x 2^-53 (1 + 2^-7) = 1.678e-16 (+ half of the rounding of x y inside e)   measured 1.360e-16
+// The seeds: v_rcp_f64 measured good to 2^-24.4 (mmpc_rcp_piv below, whose error is the seed's squared).
+// At +-0, +-inf and subnormal arguments these return NaN where 1 / x is +-inf or 0 (the edge-value table of the tests, with the call
+// sites that cannot see the difference); a NaN in gives a NaN out.
 // (MMPC_RCP_NEWTON 1: one Newton step instead of the cubic one - a dependent operation less per call, relative error e^2 resp. 3/8 e^2
-//  <= 3.6e-15; A/B switch, default off: the slacks' reciprocals enter the multipliers' update)
+//  <= 3.7e-15, measured 2.13e-15: the same tests hold it ABOVE the bound of the shipped function, as proof that they resolve one step;
+//  A/B switch, default off: the slacks' reciprocals enter the multipliers' update)
 #ifndef MMPC_RCP_NEWTON
 #define MMPC_RCP_NEWTON 0
 #endif
@@ -53,9 +60,10 @@ MMPC_DEV double mmpc_rcp(double x) {
 }
 MMPC_DEV double mmpc_rcp3(double x) { return mmpc_rcp(x); }
 // reciprocal of a pivot of the elimination legs, where every dependent operation is on the critical path of a Riccati stage: the seed
-// and ONE Newton step, r (2 - x r): relative error e^2 <= 2^-48 (3.6e-15) in two dependent fma instead of three (MMPC_PIV_NEWTON 0: the
-// cubic step of mmpc_rcp).  The factorisation it feeds is backward stable in the usual sense either way: the pivots' own rounding
-// through twenty stages of rank-one updates is of that order.
+// and ONE Newton step, r (2 - x r): relative error e^2 + one rounding <= 2^-48 + 2^-53 (3.7e-15) for a seed good to 2^-24, in two
+// dependent fma instead of three; measured 2.05e-15 = 2^-48.8 over [1e-30, 1e30] (tests/test_gpu_primitives.py; MMPC_PIV_NEWTON 0: the
+// cubic step of mmpc_rcp, measured 1.110e-16).  The factorisation it feeds is backward stable in the usual sense either way: the
+// pivots' own rounding through twenty stages of rank-one updates is of that order.
 #ifndef MMPC_PIV_NEWTON
 #define MMPC_PIV_NEWTON 1
 #endif
@@ -74,8 +82,8 @@ MMPC_DEV double mmpc_rsqrt(double x) {
 #endif
     return fma(y * e, fma(0.375, e, 0.5), y);          // y (1 + e/2 + 3 e^2/8), e = 1 - x y^2
 }
-// x^e in single precision (only used by the filter's switching rule, a heuristic threshold)
-MMPC_DEV double mmpc_powf(double x, float e) { return (double)__builtin_amdgcn_exp2f(e * __builtin_amdgcn_logf((float)x)); }
+MMPC_DEV float mmpc_log2f_raw(float x) { return __builtin_amdgcn_logf(x); }     // v_log_f32 / v_exp_f32: no subnormals in or out
+MMPC_DEV float mmpc_exp2f_raw(float x) { return __builtin_amdgcn_exp2f(x); }
 // keeps the scheduler from interleaving independent unrolled bodies (bounds the live registers)
 #ifdef MMPC_NO_SCHED_FENCE
 MMPC_DEV void mmpc_sched_fence() {}
@@ -83,6 +91,21 @@ MMPC_DEV void mmpc_sched_fence() {}
 MMPC_DEV void mmpc_sched_fence() { __builtin_amdgcn_sched_barrier(0); }
 #endif
 #endif
+
+// x^e for x >= 0 with a single-precision logarithm and exponential (only used by the filter's switching rule, a heuristic threshold:
+// relative error <= 1e-5 is its contract, ~3e-7 measured by tests/test_gpu_primitives.py).  The exponents of x and of the result are
+// carried outside the two single-precision instructions: (-dphi)^2.3 leaves the single-precision range from -dphi = 3.2e-17 down, and
+// exp2(e log2 x) in plain single precision (rounds 1-4) returned 0 there - and anything between 0 and a subnormal in the emulation -
+// where the rule compares it with th0^1.1.  An x below the smallest single-precision normal counts as 0 (as it always did on the
+// device); a negative x or a NaN gives a NaN.
+MMPC_DEV double mmpc_powf(double x, float e) {
+    if (!(x >= 1.17549435082228750797e-38)) return (x != x || x <= -1.17549435082228750797e-38) ? x + NAN : 0.0;
+    if (!(x <= 1.7976931348623157e308)) return x;
+    int k;
+    const double m = frexp(x, &k);                                                  // [0.5, 1)
+    const double t = (double)e * ((double)k + (double)mmpc_log2f_raw((float)m)), ti = rint(t);
+    return ldexp((double)mmpc_exp2f_raw((float)(t - ti)), (int)ti);
+}
 
 // product of two small non-negative integers (LDS offsets): v_mul_u32_u24 / v_mad_u32_u24 instead of the quarter-rate 32-bit multiply
 #ifdef MMPC_EMU
@@ -92,9 +115,13 @@ MMPC_DEV void mmpc_sched_fence() { __builtin_amdgcn_sched_barrier(0); }
 #endif
 
 // ---- v_mfma_f64_16x16x4_f64: D = A B + C on one wavefront.  Lane l supplies A[l&15][l>>4] and B[l>>4][l&15] and holds
-// rows (l>>4) + 4r of column l&15 of C/D in accumulator register r (tools/mfma_probe.hip checks this map on the device).
+// rows (l>>4) + 4r of column l&15 of C/D in accumulator register r.
 // An accumulator's register r is therefore K-block r (rows 4r..4r+3) of a B operand as it stands, and - for a
-// symmetric matrix - of an A operand: chained products need no lane movement.
+// symmetric matrix - of an A operand (a general matrix stands there as its transpose): chained products need no lane movement.
+// tests/test_gpu_primitives.py pins the map element by element on the device (integer operands, each element of A and B alone),
+// the chaining, and the rounding: |D - exact| <= 4 x 2^-53 (|A| |B| + |C|), measured 2.94 x 2^-53; on every real input tried (normal
+// entries; magnitudes 1e-8 .. 1e8) the device result was BITWISE that of the host macro below - four fma in ascending k - which
+// the test asserts.
 #ifdef MMPC_EMU
 struct MmpcAcc {
     double v[4];
@@ -157,7 +184,10 @@ MMPC_DEV double mmpc_lower16_f64(double v) {
 // step, tools/lat_probe.hip): the partner's value comes through DPP inside a row of 16 lanes (quad permutes for 1 and 2;
 // for 4 and 8 the half-row / row MIRROR - lane 7-i resp. 15-i holds the same value as lane i^4 resp. i^8 at that point, the
 // lanes of a reduced group being bitwise equal) and through v_permlane16_swap / v_permlane32_swap across rows.  Every lane
-// ends with the same bits (the combine is commutative), which the host emulation reproduces (mmpc_emu_red).
+// ends with the same bits (the combine is commutative), which the host emulation reproduces (mmpc_emu_red): both sentences are
+// asserted on the device, every lane of every reduction against the stand-in's bits (tests/test_gpu_primitives.py).  A NaN:
+// v_max_f64 / v_min_f64 drop it (the maximum of the other 63 lanes comes back in every lane), the stand-in's ternary keeps or
+// drops it by position; the sums return NaN in both builds.
 #endif
 #ifndef MMPC_RED_DPP
 #define MMPC_RED_DPP 1   // wave reductions through DPP / permlane swaps (steps 1..32) instead of ds_bpermute butterflies (steps 32..1)

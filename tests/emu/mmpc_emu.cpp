@@ -144,3 +144,108 @@ extern "C" int mmpc_emu_params_size() { return (int)sizeof(MmpcParams); }
 extern "C" void mmpc_emu_ik(int B, const double *q0, const double *target, double *q, int *status, int *iters) {
     for (int b = 0; b < B; b++) status[b] = mmpc_ik_solve(q0 + 3 * b, target[2 * b], target[2 * b + 1], q + 3 * b, iters + b);
 }
+
+// ---- the primitives one at a time (tests/test_primitives_cpu.py, tests/test_gpu_primitives.py): the host twin of
+// tests/gpu_prim/mmpc_prim.hip with the same entry points, item layouts and row numbers.  The scalar functions come from the
+// shared mmpc_prim_ops.h; the cross-lane exchanges, reductions and the matrix-core tile go through the stand-ins of this
+// build (MMPC_LANE_*, mmpc_emu_red / _red4 / _red_arr, the fma loops of MMPC_MFMA) exactly as the emulated solver uses them.
+#include "../gpu_prim/mmpc_prim_ops.h"
+extern "C" int mmpc_emu_prim_op_shape(int op, int *nin, int *nout) {
+    *nin = mmpc_prim_nin(op); *nout = mmpc_prim_nout(op);
+    return *nin > 0 ? 0 : -1;
+}
+extern "C" int mmpc_emu_prim_map(int op, int n, const double *in, double *out) {
+    const int nin = mmpc_prim_nin(op), nout = mmpc_prim_nout(op);
+    if (n <= 0 || nin <= 0) return -1;
+    for (int i = 0; i < n; i++) {
+        for (int j = 0; j < nout; j++) out[(size_t)i * nout + j] = 0.0;
+        mmpc_prim_map_one(op, in + (size_t)i * nin, out + (size_t)i * nout);
+    }
+    return 0;
+}
+// only the exchanges this build has a stand-in for: the rows MMPC_PRIM_LANE_READLANE + j, _XOR16, _LOWER16 (the others stay 0;
+// the roll-out's row broadcast is replaced by MMPC_LANE_GET, the butterflies' DPP steps by the partner index of mmpc_emu_red)
+struct MmpcPrimLane { double v; };
+extern "C" int mmpc_emu_prim_lanes(int nvec, const double *in, double *out) {
+    if (nvec <= 0) return -1;
+    for (int b = 0; b < nvec; b++) {
+        MmpcPrimLane ls_all[MMPC_WAVE];
+        double *o = out + (size_t)b * MMPC_PRIM_LANE_ROWS * MMPC_WAVE;
+        for (int i = 0; i < MMPC_PRIM_LANE_ROWS * MMPC_WAVE; i++) o[i] = 0.0;
+        for (int lane = 0; lane < MMPC_WAVE; lane++) ls_all[lane].v = in[(size_t)b * MMPC_WAVE + lane];
+        for (int lane = 0; lane < MMPC_WAVE; lane++) {
+            for (int j = 0; j < MMPC_WAVE; j++) o[MMPC_WAVE * (MMPC_PRIM_LANE_READLANE + j) + lane] = MMPC_LANE_GET(v, j);
+            o[MMPC_WAVE * MMPC_PRIM_LANE_XOR16 + lane] = MMPC_LANE_XOR16(v);
+            o[MMPC_WAVE * MMPC_PRIM_LANE_LOWER16 + lane] = MMPC_LANE_LOWER16(v);
+        }
+    }
+    return 0;
+}
+extern "C" int mmpc_emu_prim_red(int nvec, const double *in, double *out) {
+    if (nvec <= 0) return -1;
+    for (int b = 0; b < nvec; b++) {
+        double wr_all[MMPC_WAVE][9], RED[MMPC_WAVE], r[MMPC_PRIM_RED_ROWS];
+        for (int lane = 0; lane < MMPC_WAVE; lane++) {
+            for (int i = 0; i < 9; i++) wr_all[lane][i] = -7.0;
+            wr_all[lane][3] = RED[lane] = in[(size_t)b * MMPC_WAVE + lane];
+        }
+        r[0] = MMPC_RED_SUM(3); r[1] = MMPC_RED_MAX(3); r[2] = MMPC_RED_MIN(3);
+        r[3] = MMPC_GRED_SUM(RED); r[4] = MMPC_GRED_MAX(RED); r[5] = MMPC_GRED_MIN(RED); r[6] = MMPC_GRED_MAXERR(RED);
+        for (int q = 0; q < MMPC_PRIM_RED_ROWS; q++)   // (a value the emulated lanes share: every "lane" gets it)
+            for (int lane = 0; lane < MMPC_WAVE; lane++) out[((size_t)b * MMPC_PRIM_RED_ROWS + q) * MMPC_WAVE + lane] = r[q];
+    }
+    return 0;
+}
+extern "C" int mmpc_emu_prim_red4(int nvec, const double *in, double *out) {
+    if (nvec <= 0) return -1;
+    for (int b = 0; b < nvec; b++) {
+        double wr_all[MMPC_WAVE][9], s4[4], m4[4];
+        const double *v = in + (size_t)b * 4 * MMPC_WAVE;
+        for (int lane = 0; lane < MMPC_WAVE; lane++) {
+            for (int i = 0; i < 9; i++) wr_all[lane][i] = -7.0;
+            wr_all[lane][1] = v[lane]; wr_all[lane][4] = v[MMPC_WAVE + lane]; wr_all[lane][6] = v[2 * MMPC_WAVE + lane]; wr_all[lane][8] = v[3 * MMPC_WAVE + lane];
+        }
+        MMPC_RED4_SUM(1, 4, 6, 8, s4);
+        MMPC_RED4_MAX(1, 4, 6, 8, m4);
+        for (int j = 0; j < 4; j++)
+            for (int lane = 0; lane < MMPC_WAVE; lane++) {
+                out[((size_t)b * 8 + j) * MMPC_WAVE + lane] = s4[j]; out[((size_t)b * 8 + 4 + j) * MMPC_WAVE + lane] = m4[j];
+            }
+    }
+    return 0;
+}
+struct MmpcPrimTile { MmpcAcc acc, s, d; double a, b; };
+extern "C" int mmpc_emu_prim_mfma(int nvec, const double *in, double *out) {
+    if (nvec <= 0) return -1;
+    for (int b = 0; b < nvec; b++) {
+        MmpcPrimTile ls_all[MMPC_WAVE];
+        const double *v = in + (size_t)b * 6 * MMPC_WAVE;
+        double *o = out + (size_t)b * 8 * MMPC_WAVE;
+        for (int l = 0; l < MMPC_WAVE; l++) { ls_all[l].a = v[l]; ls_all[l].b = v[MMPC_WAVE + l]; }
+        MMPC_MFMA0(acc, ls.a, ls.b)
+        for (int l = 0; l < MMPC_WAVE; l++) for (int r = 0; r < 4; r++) { o[r * MMPC_WAVE + l] = ls_all[l].acc[r]; ls_all[l].acc[r] = v[(2 + r) * MMPC_WAVE + l]; }
+        MMPC_MFMA(acc, ls.a, ls.b)
+        for (int l = 0; l < MMPC_WAVE; l++) for (int r = 0; r < 4; r++) o[(4 + r) * MMPC_WAVE + l] = ls_all[l].acc[r];
+    }
+    return 0;
+}
+extern "C" int mmpc_emu_prim_chain(int nvec, const double *in, double *out) {
+    if (nvec <= 0) return -1;
+    for (int b = 0; b < nvec; b++) {
+        MmpcPrimTile ls_all[MMPC_WAVE];
+        const double *v = in + (size_t)b * 8 * MMPC_WAVE;
+        double *o = out + (size_t)b * 8 * MMPC_WAVE;
+        for (int l = 0; l < MMPC_WAVE; l++) for (int r = 0; r < 4; r++) { ls_all[l].s[r] = v[r * MMPC_WAVE + l]; ls_all[l].d[r] = v[(4 + r) * MMPC_WAVE + l]; }
+        MMPC_MFMA0(acc, ls.s[0], ls.d[0])
+        MMPC_MFMA(acc, ls.s[1], ls.d[1])
+        MMPC_MFMA(acc, ls.s[2], ls.d[2])
+        MMPC_MFMA(acc, ls.s[3], ls.d[3])
+        for (int l = 0; l < MMPC_WAVE; l++) for (int r = 0; r < 4; r++) o[r * MMPC_WAVE + l] = ls_all[l].acc[r];
+        MMPC_MFMA0(acc, ls.d[0], ls.s[0])
+        MMPC_MFMA(acc, ls.d[1], ls.s[1])
+        MMPC_MFMA(acc, ls.d[2], ls.s[2])
+        MMPC_MFMA(acc, ls.d[3], ls.s[3])
+        for (int l = 0; l < MMPC_WAVE; l++) for (int r = 0; r < 4; r++) o[(4 + r) * MMPC_WAVE + l] = ls_all[l].acc[r];
+    }
+    return 0;
+}
