@@ -136,9 +136,7 @@ struct MmpcParams {
 // delta_w = 0 first: in a run of corrected iterations that attempt fails nearly every time - a wasted pass; 0.75 fewer passes per solve)
 #define MMPC_IC_SKIP0 0.1
 // second-order corrections per iteration (IPOPT: max_soc = 4), tried where theta(x_k) <= theta_min
-#ifndef MMPC_SOC_MAX
 #define MMPC_SOC_MAX 2
-#endif
 #define MMPC_PROX_LO 0.05
 #define MMPC_PROX_MAX 1e4
 // multiplier safeguard (IPOPT eq. 16): z_i is kept within [mu / (kappa t_i), kappa mu / t_i] at every evaluation
@@ -211,9 +209,6 @@ struct MmpcDims {
 #ifndef MMPC_GEN_RIC_UNROLL
 #define MMPC_GEN_RIC_UNROLL 2
 #endif
-#ifndef MMPC_GEN_TILE
-#define MMPC_GEN_TILE 1   // the generic kernel's Riccati pass on v_mfma_f64_16x16x4_f64 tiles (as the specialised kernel's); 0: scalar pass through LDS
-#endif
 #define MMPC_NBC 3   // border columns: terminal multipliers nu0, nu1 and the slack s_{N-1} of the NLP as written (see A2)
 // LDS slab layout (offsets in doubles).  Shared by host (size query) and device.
 struct MmpcLayout {
@@ -251,7 +246,7 @@ MMPC_HD constexpr MmpcLayout mmpc_layout(int N, int M, int obs_per_stage, int nh
     // (interface_wholebody_qref.py:166-167) and the slack s_{N-1} when it reaches back to x_{N-2} (NLP as written): sensitivities
     MMPC_CARVE(PNU, D::NX * MMPC_NBC) MMPC_CARVE(PNUS, NS * D::NX * MMPC_NBC) MMPC_CARVE(KFV, N * D::NU * MMPC_NBC) MMPC_CARVE(GNU, D::NV * MMPC_NBC)
     MMPC_CARVE(FWV, 2 * (1 + MMPC_NBC) * D::NX) MMPC_CARVE(NUEQ, 4) MMPC_CARVE(GHS, NS * nhs * 6) MMPC_CARVE(WTS, MMPC_W_SIZE) MMPC_CARVE(SIGW, 16)
-    MMPC_CARVE(KU, MMPC_GEN_TILE ? N * (D::NU * (D::NU - 1) / 2) : 0) MMPC_CARVE(PIV, MMPC_GEN_TILE ? N * D::NU : 0)
+    MMPC_CARVE(KU, N * (D::NU * (D::NU - 1) / 2)) MMPC_CARVE(PIV, N * D::NU)
     // as-written rows: gradient / branch per row; per stage: coupling of s_k to x_{k-1}, what stage k's rows add to stage k-1
     // (residual, Hessian y-block, gradient), dense blocks of a slack eliminated one stage earlier, x-stationarity residual
     MMPC_CARVE(GQ8, NS * nq * 6) MMPC_CARVE(BQ8, NS * nq) MMPC_CARVE(VQ, nq ? NS * 6 : 0) MMPC_CARVE(RQ, nq ? (NS + 1) * 6 : 0)
@@ -299,15 +294,11 @@ MMPC_DEV double mmpc_max_err(double a, double b) { return (a > b || a != a) ? a 
 #define MMPC_GRED_MIN(ARR) mmpc_emu_red_arr((ARR), 2)
 #define MMPC_GRED_MAXERR(ARR) mmpc_emu_red_arr((ARR), 3)
 #else
-#if MMPC_RED_DPP
 MMPC_DEV double mmpc_gop_add(double a, double b) { return a + b; }
 MMPC_WAVE_RED(mmpc_gwave_sum, mmpc_gop_add)
 MMPC_WAVE_RED(mmpc_gwave_max, mmpc_max)
 MMPC_WAVE_RED(mmpc_gwave_min, mmpc_min)
 MMPC_WAVE_RED(mmpc_gwave_maxerr, mmpc_max_err)
-#else
-#error "the generic kernel's reductions need MMPC_RED_DPP"
-#endif
 #define MMPC_GRED_SUM(ARR) mmpc_gwave_sum((ARR)[mmpc_lane_id()])
 #define MMPC_GRED_MAX(ARR) mmpc_gwave_max((ARR)[mmpc_lane_id()])
 #define MMPC_GRED_MIN(ARR) mmpc_gwave_min((ARR)[mmpc_lane_id()])
@@ -358,17 +349,12 @@ MMPC_DEV void mmpc_sincos(double x, double *sn, double *cs) {
     *sn = (q & 2) ? -sa : sa;
     *cs = ((q + 1) & 2) ? -ca : ca;
 }
-#ifndef MMPC_LIBM_SINCOS
-#define MMPC_SINCOS(x, s, c) mmpc_sincos((x), (s), (c))
-#else
-#define MMPC_SINCOS(x, s, c) sincos((x), (s), (c))
-#endif
 // planar arm segments, manipulator_3DoF.py:29-73 collapsed with A=q1-q2, B=q1-q2-q3
 MMPC_DEV void mmpc_arm_segments(double q1, double q2, double q3, double dr[3], double dz[3]) {
     double s1, c1, sA, cA, sB, cB;
-    MMPC_SINCOS(q1, &s1, &c1);
-    MMPC_SINCOS(q1 - q2, &sA, &cA);
-    MMPC_SINCOS(q1 - q2 - q3, &sB, &cB);
+    mmpc_sincos(q1, &s1, &c1);
+    mmpc_sincos(q1 - q2, &sA, &cA);
+    mmpc_sincos(q1 - q2 - q3, &sB, &cB);
     dr[0] = MMPC_A2 * s1 + MMPC_A3 * c1;
     dz[0] = MMPC_A2 * c1 - MMPC_A3 * s1;
     dr[1] = -MMPC_A3 * cA + MMPC_A5 * sA;
@@ -528,7 +514,7 @@ MMPC_DEV double mmpc_state_cost(const double *WTS, bool terminal, const double *
         return q;
     } else {
     double sn, cs, dr[3], dz[3];
-    MMPC_SINCOS(xk[2], &sn, &cs);
+    mmpc_sincos(xk[2], &sn, &cs);
     mmpc_arm_segments(xk[NX - 3], xk[NX - 2], xk[NX - 1], dr, dz);
     const double R = MMPC_BX + dr[0] + dr[1] + dr[2], Z = MMPC_BZ + dz[0] + dz[1] + dz[2];
     const double e[4] = {xk[0] + R * cs - ref[0], xk[1] + R * sn - ref[1], Z - ref[2], xk[2] - ref[3]};
@@ -574,7 +560,6 @@ MMPC_DEV double mmpc_state_cost(const double *WTS, bool terminal, const double *
 // the whole solve - they spill to vector lanes, and those to scratch; instantiated for a shape they are constants.
 // NC, MC, OPSC, LC, AWC: horizon, circle obstacles, obs_per_stage, half-space planes and the as-written flag when they are
 // constants of the instantiation (the demo's shapes: every LDS offset is then an immediate), 0 / -1: read from the parameter block
-#if MMPC_GEN_TILE
 // lane state of the Riccati pass on MFMA tiles (lane = 16 g + j; accumulator register r <-> row g + 4 r, column j of the
 // 16x16 tile over (x, 1, u)); the same fields as the specialised kernel's MmpcLaneState (mmpc_fast.h)
 template <int KIND>
@@ -598,7 +583,6 @@ struct MmpcGenRic {
     double rAB[NKB], opa, opb;           // MFMA operands
     double nab[NKB], nhm[4];             // next stage's dynamics rows and stage-matrix entries
 };
-#endif
 
 template <int KIND, int NC = 0, int MC = -1, int OPSC = -1, int LC = -1, int AWC = -1>
 MMPC_DEV void mmpc_solve_one(const MmpcParams &P, const MmpcIO io, double *lds MMPC_EMU_ARG) {
@@ -728,14 +712,14 @@ MMPC_DEV void mmpc_solve_one(const MmpcParams &P, const MmpcIO io, double *lds M
         }
         if (NSELF) {
             double dr[3], dz[3], sn, cs;
-            MMPC_SINCOS(xk[2], &sn, &cs);
+            mmpc_sincos(xk[2], &sn, &cs);
             mmpc_arm_segments(xk[NX - 3], xk[NX - 2], xk[NX - 1], dr, dz);
             for (int i = 0; i < NSELF; i++) hr[M + i] = mmpc_self_row(i, xk[0], xk[1], cs, sn, dr, dz, nullptr) - sks;
             for (int i = 0; i < NHS; i++) hr[M + NSELF + i] = mmpc_hs_row(P, i, xk[0], xk[1], cs, sn, dr, dz, nullptr) - sk;
             if (NQ && k >= 1) {
                 const double *xp = X + (k - 1) * NX;
                 double drp[3], dzp[3], snp, csp;
-                MMPC_SINCOS(xp[2], &snp, &csp);
+                mmpc_sincos(xp[2], &snp, &csp);
                 mmpc_arm_segments(xp[NX - 3], xp[NX - 2], xp[NX - 1], drp, dzp);
                 for (int e = 0; e < NQ; e++) { int br; hr[M + NSELF + NHS + e] = q8_row(e, xk, cs, sn, dr, dz, xp, csp, snp, drp, dzp, br, nullptr, nullptr) - sk; }
             }
@@ -770,7 +754,6 @@ MMPC_DEV void mmpc_solve_one(const MmpcParams &P, const MmpcIO io, double *lds M
 
     int status = 1, it = 0, nfilt = 0, filt_init = 0, nrows_act = 0, nsmall = 0;
     double prox = 0.0, delta_last = 0.0, delta_prev = 0.0;   // (delta_prev: the correction of the previous iteration's matrix, 0 when it needed none)
-#if MMPC_GEN_TILE
     // Riccati recursion on MFMA tiles over (x, 1, u), as in mmpc_fast.h (see there for the lane <-> entry map): lane l = 16 g + j
     // holds rows g + 4 r of column j in accumulator register r
     typedef MmpcGenRic<KIND> GR;
@@ -809,7 +792,7 @@ MMPC_DEV void mmpc_solve_one(const MmpcParams &P, const MmpcIO io, double *lds M
             ls.p_o[r] = off; ls.p_s[r] = stride;
         }
         for (int r = 0; r < 4; r++) {
-            // entry (ti, tj) of a stage's matrix [Hxx Hxu q_x; Hux Huu q_u; q^T 0] in tile numbering (what R2 of the scalar pass adds
+            // entry (ti, tj) of a stage's matrix [Hxx Hxu q_x; Hux Huu q_u; q^T 0] in tile numbering (what R2 adds
             // to [A B]^T P [A B]), as the sum - in this order - of up to four words: packed Hxx; gradient in row / column NX;
             // Hux = dense block of a slack eliminated at the last stage (quirk Q1) + the same of the as-written rows (any stage) + the
             // (0,2) entry of the dynamics curvature; Huu = R2 + W2 + diagonal barrier terms + the two dense blocks.  An absent term
@@ -893,7 +876,6 @@ MMPC_DEV void mmpc_solve_one(const MmpcParams &P, const MmpcIO io, double *lds M
         }
     }
     LANES_END
-#endif
     double E0 = 0.0, th_max = 0.0, th_min = 0.0;
     // number of active rows (uniform): box rows that exist + all non-box rows
     for (int r = 0; r < SL_C; r++) {
@@ -918,7 +900,7 @@ MMPC_DEV void mmpc_solve_one(const MmpcParams &P, const MmpcIO io, double *lds M
             double mant = 1.0; int ex = 0;   // product of the mantissas of the stage's slacks + sum of their exponents (one log per stage)
             auto acc = [&](double tv) { int e2; mant *= frexp(tv, &e2); ex += e2; if (mant < 1e-200) { mant = frexp(mant, &e2); ex += e2; } };
             double sn, cs;
-            MMPC_SINCOS(xk[2], &sn, &cs);
+            mmpc_sincos(xk[2], &sn, &cs);
             double rdx[NX], rdu[NU > 0 ? NU : 1];
             // cost gradient (mpc_wholebody_qref.py:192-201,240-242; mpc_base.py:146-153)
             {
@@ -1029,7 +1011,7 @@ MMPC_DEV void mmpc_solve_one(const MmpcParams &P, const MmpcIO io, double *lds M
                     if (k >= 1) {
                         const double *xp = X + (k - 1) * NX;
                         double drp[3], dzp[3], snp, csp;
-                        MMPC_SINCOS(xp[2], &snp, &csp);
+                        mmpc_sincos(xp[2], &snp, &csp);
                         mmpc_arm_segments(xp[NX - 3], xp[NX - 2], xp[NX - 1], drp, dzp);
                         for (int e = 0; e < NQ; e++) {
                             double g6[6];
@@ -1268,7 +1250,7 @@ MMPC_DEV void mmpc_solve_one(const MmpcParams &P, const MmpcIO io, double *lds M
                 double snF = 0.0, csF = 1.0, drF[3] = {0, 0, 0}, dzF[3] = {0, 0, 0};
                 if (exact && NHS > 0) {
                     const double *xk = X + k * NX;
-                    MMPC_SINCOS(xk[2], &snF, &csF);
+                    mmpc_sincos(xk[2], &snF, &csF);
                     mmpc_arm_segments(xk[NX - 3], xk[NX - 2], xk[NX - 1], drF, dzF);
                 }
                 for (int i = 0; i < NHS; i++) {
@@ -1311,7 +1293,7 @@ MMPC_DEV void mmpc_solve_one(const MmpcParams &P, const MmpcIO io, double *lds M
                         if (exact) {
                             sn = snF; cs = csF;
                             for (int a = 0; a < 3; a++) { dr[a] = drF[a]; dz[a] = dzF[a]; }
-                            MMPC_SINCOS(xp[2], &snp, &csp); mmpc_arm_segments(xp[NX - 3], xp[NX - 2], xp[NX - 1], drp, dzp);
+                            mmpc_sincos(xp[2], &snp, &csp); mmpc_arm_segments(xp[NX - 3], xp[NX - 2], xp[NX - 1], drp, dzp);
                         }
                         for (int e = 0; e < NQ; e++) {
                             const double t = T[k * R + SL_Q + e], z = Z[k * R + SL_Q + e], w = z / t;
@@ -1460,10 +1442,9 @@ MMPC_DEV void mmpc_solve_one(const MmpcParams &P, const MmpcIO io, double *lds M
             const bool brd = teq || sig;                  // border columns in play
             // y-entry of a state index (x, y, psi, q1, q2, q3 <-> 0..5), -1: none
             auto yix = [&](int i) -> int { return i < 3 ? i : (i >= NX - 3 ? i - (NX - 6) : -1); };
-#if MMPC_GEN_TILE
             {
-                // entry (ti, tj) of stage k's matrix [Hxx Hxu q_x; Hux Huu q_u; q^T 0] in tile numbering (what R2 of the scalar
-                // pass adds to [A B]^T P [A B]): packed Hxx; Hux = (0,2) entry of the dynamics curvature + the dense blocks of a
+                // entry (ti, tj) of stage k's matrix [Hxx Hxu q_x; Hux Huu q_u; q^T 0] in tile numbering (what R2 adds to
+                // [A B]^T P [A B]): packed Hxx; Hux = (0,2) entry of the dynamics curvature + the dense blocks of a
                 // slack eliminated here (last stage: quirk Q1; as-written rows: any stage); Huu = R2 + W2 + diagonal barrier terms
                 // + the same dense blocks; gradient in row / column NX
                 auto stage_entry = [&](const unsigned (&t)[4], const int k) -> double {
@@ -1603,7 +1584,7 @@ MMPC_DEV void mmpc_solve_one(const MmpcParams &P, const MmpcIO io, double *lds M
                         // (two short phases per stage - bp by one lane per (column, input), p_k by one lane per (column, state), both
                         //  reading p_{k+1} from its stored copy - and the kf of all stages and columns in one phase afterwards: the
                         //  same sums in the same order as one lane per column would form them, a third of the time)
-                        double *const BPS = GNU;   // (the scalar pass's array: NV x NBC >= NBC x NU doubles)
+                        double *const BPS = GNU;   // (NV x NBC >= NBC x NU doubles)
                         for (int k = N - 1; k >= 0; k--) {
                             const double *cv = CV + k * MMPC_NCV;
                             const double *pn = PNUS + (k + 1) * NX * MMPC_NBC;
@@ -1653,153 +1634,6 @@ MMPC_DEV void mmpc_solve_one(const MmpcParams &P, const MmpcIO io, double *lds M
                 }
                 MMPC_GS2(5)
             }
-#else
-            LANES_BEGIN
-            for (int e = lane; e < NX * NX; e += MMPC_WAVE) {
-                const int i = e / NX, j = e % NX;
-                PF[e] = HXX[N * NXX + (i >= j ? i * (i + 1) / 2 + j : j * (j + 1) / 2 + i)] + ((teq && i == j && i < 2) ? MMPC_RHO_EQ : 0.0);
-            }
-            if (brd)
-                for (int e = lane; e < NX * MMPC_NBC; e += MMPC_WAVE) {   // p_N of the border columns: E^T (E = [I2 0]) and -vN
-                    const int i = e / MMPC_NBC, c = e % MMPC_NBC;
-                    double v = 0.0;
-                    if (c < 2) v = (teq && i == c) ? 1.0 : 0.0;
-                    else if (sig && yix(i) >= 0) v = -VXN[yix(i)];
-                    PNU[e] = v; PNUS[N * NX * MMPC_NBC + e] = v;
-                }
-            LANES_END
-            // ---- Riccati recursion (block LDL^T of the stage-wise KKT matrix)
-            for (int k = N - 1; k >= 0; k--) {
-                const double *cv = CV + k * MMPC_NCV;
-                // R1: T = P [A B],  pc = p + P c
-                LANES_BEGIN
-                for (int e = lane; e < NX * NV + NX; e += MMPC_WAVE) {
-                    if (e < NX * NV) {
-                        const int i = e / NV, j = e % NV;
-                        double v = 0.0;
-                        for (int q = 0; q < 4; q++) v += PF[i * NX + TB::crow(j, q)] * cv[TB::ccv(j, q)];
-                        TT[e] = v;
-                    } else {
-                        const int i = e - NX * NV;
-                        double v = QX[(k + 1) * NX + i];
-                        if (teq && k == N - 1 && i < 2) v -= MMPC_RHO_EQ * (XREF[N * NX + i] - X[N * NX + i]);
-                        for (int m = 0; m < NX; m++) v += PF[i * NX + m] * CD[k * NX + m];
-                        PC[i] = v;
-                    }
-                }
-                LANES_END
-                // R2: [F G^T; G Hh] = [A B]^T T + stage Hessian;  [gx; gu] = q + [A B]^T pc
-                LANES_BEGIN
-                for (int e = lane; e < NXX + NU * NX + NUU + NV; e += MMPC_WAVE) {
-                    if (e < NXX) {
-                        const int i = kTriI[e], j = kTriJ[e];
-                        double v = HXX[k * NXX + e];
-                        for (int q = 0; q < 4; q++) v += cv[TB::ccv(i, q)] * TT[TB::crow(i, q) * NV + j];
-                        MF[e] = v;
-                    } else if (e < NXX + NU * NX) {
-                        const int e2 = e - NXX, a = e2 / NX, j = e2 % NX, col = NX + a;
-                        double v = (k == N - 1 ? HUXL[e2] : 0.0) + (NQ ? HUXS[k * NU * NX + e2] : 0.0) + ((a == 0 && j == 2) ? HUX02[k] : 0.0);
-                        for (int q = 0; q < 4; q++) v += cv[TB::ccv(col, q)] * TT[TB::crow(col, q) * NV + j];
-                        MG[e2] = v;
-                    } else if (e < NXX + NU * NX + NUU) {
-                        const int e2 = e - NXX - NU * NX, a = kTriI[e2], b = kTriJ[e2], col = NX + a;
-                        double v = WTS[MMPC_W_RW2 + a * NU + b] + (a == b ? HUUD[k * NU + a] : 0.0) + (k == N - 1 ? HUUL[e2] : 0.0) + (NQ ? HUUS[k * NUU + e2] : 0.0);
-                        for (int q = 0; q < 4; q++) v += cv[TB::ccv(col, q)] * TT[TB::crow(col, q) * NV + NX + b];
-                        MH[e2] = v;
-                    } else {
-                        const int j = e - NXX - NU * NX - NUU;
-                        double v = j < NX ? QX[k * NX + j] : QU[k * NU + j - NX];
-                        for (int q = 0; q < 4; q++) v += cv[TB::ccv(j, q)] * PC[TB::crow(j, q)];
-                        if (j < NX) MGX[j] = v; else MGU[j - NX] = v;
-                    }
-                }
-                if (brd)
-                    for (int e = lane; e < NV * MMPC_NBC; e += MMPC_WAVE) {   // g = [A B]^T p_{k+1} of the border columns (+ -v~ of this stage)
-                        const int j = e / MMPC_NBC, c = e % MMPC_NBC;
-                        double v = 0.0;
-                        for (int q = 0; q < 4; q++) v += cv[TB::ccv(j, q)] * PNU[TB::crow(j, q) * MMPC_NBC + c];
-                        if (c == 2 && sig && j < NX && yix(j) >= 0) {
-                            if (k == N - 1) v -= VX[(N - 1) * 6 + yix(j)];
-                            if (k == N - 2) v -= VQ[(N - 1) * 6 + yix(j)];
-                        }
-                        GNU[e] = v;
-                    }
-                LANES_END
-                // R3/R4: Cholesky of Hh (every solving lane redundantly, in registers), then one
-                //        right-hand side per lane: K = -Hh^{-1} G (NX columns), kf = -Hh^{-1} gu
-                LANES_BEGIN
-                if (lane <= NX + (brd ? MMPC_NBC : 0)) {
-                    double Lc[NUU];
-                    bool ok = true;
-#pragma unroll
-                    for (int j = 0; j < NU; j++) {
-                        double d = MH[j * (j + 1) / 2 + j];
-#pragma unroll
-                        for (int q = 0; q < j; q++) d -= Lc[j * (j + 1) / 2 + q] * Lc[j * (j + 1) / 2 + q];
-                        if (!(d > 0.0) || !mmpc_finite(d)) { ok = false; d = 1.0; }
-                        const double ljj = sqrt(d), il = 1.0 / ljj;
-                        Lc[j * (j + 1) / 2 + j] = il;  // store the inverse pivot
-#pragma unroll
-                        for (int i = j + 1; i < NU; i++) {
-                            double v = MH[i * (i + 1) / 2 + j];
-#pragma unroll
-                            for (int q = 0; q < j; q++) v -= Lc[i * (i + 1) / 2 + q] * Lc[j * (j + 1) / 2 + q];
-                            Lc[i * (i + 1) / 2 + j] = v * il;
-                        }
-                    }
-                    double rhs[NU];
-#pragma unroll
-                    for (int a = 0; a < NU; a++) rhs[a] = lane < NX ? MG[a * NX + lane] : (lane == NX ? MGU[a] : GNU[(NX + a) * MMPC_NBC + lane - NX - 1]);
-#pragma unroll
-                    for (int i = 0; i < NU; i++) {
-                        double v = rhs[i];
-#pragma unroll
-                        for (int q = 0; q < i; q++) v -= Lc[i * (i + 1) / 2 + q] * rhs[q];
-                        rhs[i] = v * Lc[i * (i + 1) / 2 + i];
-                    }
-#pragma unroll
-                    for (int i = NU - 1; i >= 0; i--) {
-                        double v = rhs[i];
-#pragma unroll
-                        for (int q = i + 1; q < NU; q++) v -= Lc[q * (q + 1) / 2 + i] * rhs[q];
-                        rhs[i] = v * Lc[i * (i + 1) / 2 + i];
-                    }
-#pragma unroll
-                    for (int a = 0; a < NU; a++) {
-                        if (lane < NX) KK[(k * NU + a) * NX + lane] = -rhs[a];
-                        else if (lane == NX) KF[k * NU + a] = -rhs[a];
-                        else KFV[(k * NU + a) * MMPC_NBC + lane - NX - 1] = -rhs[a];
-                    }
-                    if (!ok && lane == 0) MISC[0] = 1.0;
-                }
-                LANES_END
-                if (MISC[0] != 0.0) { failed = 1; break; }
-                // R5: P_k = F + G^T K,  p_k = gx + G^T kf   (overwrite the stage blocks)
-                LANES_BEGIN
-                if (brd)
-                    for (int e = lane; e < NX * MMPC_NBC; e += MMPC_WAVE) {   // p_k = g_x + G^T kf of the border columns
-                        const int i = e / MMPC_NBC, c = e % MMPC_NBC;
-                        double v = GNU[i * MMPC_NBC + c];
-                        for (int a = 0; a < NU; a++) v += MG[a * NX + i] * KFV[(k * NU + a) * MMPC_NBC + c];
-                        PNU[e] = v; PNUS[k * NX * MMPC_NBC + e] = v;
-                    }
-                for (int e = lane; e < NXX + NX; e += MMPC_WAVE) {
-                    if (e < NXX) {
-                        const int i = kTriI[e], j = kTriJ[e];
-                        double v = MF[e];
-                        for (int a = 0; a < NU; a++) v += MG[a * NX + i] * KK[(k * NU + a) * NX + j];
-                        HXX[k * NXX + e] = v;
-                        PF[i * NX + j] = v; PF[j * NX + i] = v;
-                    } else {
-                        const int i = e - NXX;
-                        double v = MGX[i];
-                        for (int a = 0; a < NU; a++) v += MG[a * NX + i] * KF[k * NU + a];
-                        QX[k * NX + i] = v;
-                    }
-                }
-                LANES_END
-            }
-#endif
             if (!failed && brd) {
                 // the direction is affine in the border variables y = (nu0, nu1, dsigma): roll out the y = 0 solution and the
                 // sensitivities (same gains K; homogeneous dynamics for the sensitivities), and collect v~.d of every column
@@ -1816,7 +1650,6 @@ MMPC_DEV void mmpc_solve_one(const MmpcParams &P, const MmpcIO io, double *lds M
                         const double *cv = CV + k * MMPC_NCV;
                         const double *d = src + c * NX;
                         double v = c == 0 ? CD[k * NX + i] : 0.0;
-#if MMPC_GEN_TILE
                         {   // (row i of [A B] from the two packed words of the lane: state terms, then the input term - the tables' order)
                             const unsigned st = MMPC_LS.fwb_st, fi = MMPC_LS.fwb_in;
                             const int a = (int)(fi & 255u) - 1;
@@ -1827,19 +1660,6 @@ MMPC_DEV void mmpc_solve_one(const MmpcParams &P, const MmpcIO io, double *lds M
                                 v += cv[(fi >> 8) & 255u] * x;
                             }
                         }
-#else
-                        for (int q = 0; q < 5; q++) {
-                            const int col = TB::rcol(i, q);
-                            double x;
-                            if (col < NX) x = d[col];
-                            else {
-                                const int a = col - NX;
-                                x = c == 0 ? KF[k * NU + a] : KFV[(k * NU + a) * MMPC_NBC + c - 1];
-                                for (int j = 0; j < NX; j++) x += KK[(k * NU + a) * NX + j] * d[j];
-                            }
-                            v += cv[TB::rcv(i, q)] * x;
-                        }
-#endif
                         dst[c * NX + i] = v;
                     }
                     LANES_END
@@ -1914,7 +1734,6 @@ MMPC_DEV void mmpc_solve_one(const MmpcParams &P, const MmpcIO io, double *lds M
         LANES_BEGIN
         for (int j = lane; j < NX; j += MMPC_WAVE) DX[j] = 0.0;
         LANES_END
-#if MMPC_GEN_TILE
         // (one phase per stage: the lane of row i forms the input step its row needs itself - nine products - instead of waiting for
         //  another lane's through LDS, and takes its row of [A B] from two packed words set once: the table look-ups by lane index
         //  were vector loads from constant memory in every stage)
@@ -1938,28 +1757,6 @@ MMPC_DEV void mmpc_solve_one(const MmpcParams &P, const MmpcIO io, double *lds M
             }
             LANES_END
         }
-#else
-        for (int k = 0; k < N; k++) {
-            LANES_BEGIN
-            if (lane < NU) {
-                double v = KF[k * NU + lane];
-                for (int j = 0; j < NX; j++) v += KK[(k * NU + lane) * NX + j] * DX[k * NX + j];
-                DU[k * NU + lane] = v;
-            }
-            LANES_END
-            LANES_BEGIN
-            if (lane < NX) {
-                const double *cv = CV + k * MMPC_NCV;
-                double v = CD[k * NX + lane];
-                for (int q = 0; q < 5; q++) {
-                    const int c = TB::rcol(lane, q);
-                    v += cv[TB::rcv(lane, q)] * (c < NX ? DX[k * NX + c] : DU[k * NU + c - NX]);
-                }
-                DX[(k + 1) * NX + lane] = v;
-            }
-            LANES_END
-        }
-#endif
         MMPC_GS(4)
         // ---- D1: multiplier step and slack-variable step
         LANES_BEGIN
@@ -2002,7 +1799,7 @@ MMPC_DEV void mmpc_solve_one(const MmpcParams &P, const MmpcIO io, double *lds M
             double f = Sw * sk * sk, th = 0.0;
             f += 0.5 * mmpc_state_cost<KIND>(WTS, k == N, xk, XREF + k * NREF, nullptr, nullptr, false);
             double sn, cs;
-            MMPC_SINCOS(xk[2], &sn, &cs);
+            mmpc_sincos(xk[2], &sn, &cs);
             if (k < N) {
                 for (int a = 0; a < NU; a++) uk[a] = U[k * NU + a] + alpha * DU[k * NU + a];
                 double q = 0.0;
@@ -2055,7 +1852,7 @@ MMPC_DEV void mmpc_solve_one(const MmpcParams &P, const MmpcIO io, double *lds M
                     if (NQ && k >= 1) {
                         double xp[NX], drp[3], dzp[3], snp, csp;
                         for (int j = 0; j < NX; j++) xp[j] = X[(k - 1) * NX + j] + alpha * DX[(k - 1) * NX + j];
-                        MMPC_SINCOS(xp[2], &snp, &csp);
+                        mmpc_sincos(xp[2], &snp, &csp);
                         mmpc_arm_segments(xp[NX - 3], xp[NX - 2], xp[NX - 1], drp, dzp);
                         for (int e = 0; e < NQ; e++) { int br; hr[M + NSELF + NHS + e] = q8_row(e, xk, cs, sn, dr, dz, xp, csp, snp, drp, dzp, br, nullptr, nullptr) - sk; }
                     }

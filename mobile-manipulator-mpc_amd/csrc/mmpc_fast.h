@@ -18,6 +18,26 @@
 // Written in the same PHASE discipline as mmpc_core.h so that -DMMPC_EMU builds run it on the
 // host (tests only); lane-private state that survives a phase lives in `LS` (struct per lane)
 // and `WR` (reduction inputs).
+//
+// Build switches of csrc/ (switch: what it selects; shipped value; who builds the other value).  The rule: a switch without such
+// a user does not stay in csrc/ - the losing side of a settled A/B experiment is deleted, its measurement stays in DESIGN.md.
+//   MMPC_EMU                    host lane emulation of both kernels instead of device code; off; tests/emu (every CPU test of the kernels)
+//   MMPC_EMU_DEBUG              the emulation reports lost pivots and failed steps on stderr; off; by hand with tests/emu
+//   MMPC_PADMAP                 padded pair map (MmpcFastDims::PADMAP) or the plain one; 1; tests/test_emu_variants.py
+//   MMPC_LEG_DET                second pivot of a pair leg from the 2 x 2 determinant or sequentially; 1; tests/test_emu_variants.py
+//   MMPC_D2_ONE_RCP             row steps D2 with one reciprocal per row or two; 1; tests/test_emu_variants.py
+//   MMPC_SAFEGUARD_LAZY         multiplier safeguard of the first trial as a range check or always exact; 1; tests/test_emu_variants.py
+//   MMPC_SAFEGUARD_FORCE        the exact clamp after every first trial; off; tests/test_emu_variants.py
+//   MMPC_RCP_NEWTON             mmpc_rcp / mmpc_rsqrt with a Newton step instead of the cubic one; 0; tests/test_gpu_primitives.py,
+//                               tests/test_primitives_cpu.py (the library is built by the entry point's build())
+//   MMPC_PIV_NEWTON             mmpc_rcp_piv with one Newton step or the cubic step of mmpc_rcp; 1; the same tests
+//   MMPC_STAMP, _STAMP_COARSE   per-phase cycle stamps of the specialised kernel (without those inside the stage loop); off; tools/probe_stamps.py
+//   MMPC_STAMP_GEN, _GEN_A, _GEN_E   the same for the generic kernel (slots 10..15: assembly / evaluation pieces); off; tools/probe_stamps_generic.py
+//   MMPC_PHASE_SYNC             __syncthreads() at every phase end instead of the wavefront-scope fence; off; tools/sync_check.py
+//   MMPC_FAST_LIST, MMPC_STATIC_LIST   the instantiation lists of mmpc_hip.hip; the full lists; tools/build_variant.sh, tools/occupancy_probe.sh
+//   MMPC_SLIM_NMIN 21, MMPC_GAINS_GLOBAL_NMIN, MMPC_RG_NMIN (both MMPC_SLIM_NMIN), MMPC_RG_MAX 3, MMPC_UNROLL_NMAX 30, MMPC_RIC_UNROLL 2,
+//   MMPC_FWD_UNROLL 64, MMPC_GEN_RIC_UNROLL 2, MMPC_GEN_FWD_UNROLL 2: layout and unrolling constants (defined where they are used, with
+//                               their measurements); the values named here; tools/build_variant.sh <tag> -D..., the way in for the next kernel work
 #pragma once
 #include "mmpc_core.h"
 
@@ -40,15 +60,6 @@ __device__ unsigned long long mmpc_stamp_acc[16];
 #define MMPC_TS(i)
 #define MMPC_TSF(i)
 #define MMPC_TEND()
-#endif
-// A wave's stores to global memory (the gain block of long horizons) followed by loads of the same words from other lanes of the
-// SAME wave: the vector memory instructions of a wavefront are issued and processed in order, so the wavefront-scope fence of
-// LANES_END (compiler ordering only, no s_waitcnt) is all that is needed - waiting for the stores' acknowledgement here cost 2 x
-// ~1 k cycles per iteration (-DMMPC_GFENCE_WG restores the workgroup-scope fence for A/B checks).
-#if defined(MMPC_GFENCE_WG) && !defined(MMPC_EMU)
-#define MMPC_GFENCE() { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup"); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup"); }
-#else
-#define MMPC_GFENCE()
 #endif
 #define MMPC_MC_MAX 8    // largest number of circle rows the register-resident path is instantiated for
 
@@ -118,25 +129,14 @@ MMPC_DEV double mmpc_box_t(double d) { return mmpc_vmax(d, 1e-15); }
 #ifndef MMPC_SAFEGUARD_LAZY
 #define MMPC_SAFEGUARD_LAZY 1   // multiplier safeguard of the first trial: range check per row, exact clamp only if some row needs it (see apply_step; A/B switch)
 #endif
-// scheduler fences of this file by site: bit i of MMPC_FENCE_MASK keeps fence i (0 init, 1 trial move pairs, 2 E1 stage loads, 3 / 4 E1 pair
-// pass / loads, 5 / 6 A1 pair pass / loads, 7 leg before the product, 8 D1 loads, 9 A1 stage loads, 10 D2 pairs).  A lone wave issues a
-// dependent instruction every ~8 cycles and an independent one every ~4: fences that keep the unrolled bodies of a lane-parallel loop
-// apart (rounds 1-3: fewer live registers) cost more in issue bubbles than the register moves they save.
-#ifndef MMPC_FENCE_MASK
-#define MMPC_FENCE_MASK 0x000
-#endif
-#define MMPC_SFENCE(i) { if ((MMPC_FENCE_MASK >> (i)) & 1) mmpc_sched_fence(); }
-#ifndef MMPC_TRGS
-#define MMPC_TRGS 9      // stride of the per-stage trig cache (8 words used): with 8 the stage lanes' words sit 16 dwords apart - two LDS banks for 21 lanes
-#endif
+// (Scheduler fences between the unrolled bodies of the lane-parallel loops - fewer live registers in rounds 1-3 - were tried at eleven
+// sites and removed: a lone wave issues a dependent instruction every ~8 cycles and an independent one every ~4, and the fences cost
+// 3.6 % in issue bubbles, more than the register moves they saved.)
 #ifndef MMPC_LEG_DET
 #define MMPC_LEG_DET 1    // pair legs: the second pivot's reciprocal from the 2 x 2 determinant, beside the first's (A/B switch)
 #endif
 #ifndef MMPC_D2_ONE_RCP
 #define MMPC_D2_ONE_RCP 1   // row steps D2: one reciprocal per row (see mmpc_fast_d2.inc; A/B switch)
-#endif
-#ifndef MMPC_FWD_DPP
-#define MMPC_FWD_DPP 1   // forward roll-out: dx_k by v_mov_b64_dpp row_newbcast instead of v_readlane pairs (A/B switch)
 #endif
 #ifndef MMPC_PADMAP
 #define MMPC_PADMAP 1    // padded pair map (see MmpcFastDims::PADMAP); 0: the plain map everywhere (A/B switch)
@@ -162,8 +162,9 @@ struct MmpcFastDims {
     // column l & 15 < NV is the variable; the pairs of the terminal stage (states only) sit in column NV of the first NX rows.  Every
     // address is then base(l) + p * stride(l), both formed once per phase.
     static constexpr bool PADMAP = MMPC_PADMAP && NV < 16 && NX <= N && (N * 16 + MMPC_WAVE - 1) / MMPC_WAVE <= (NPAIR + MMPC_WAVE - 1) / MMPC_WAVE;
-    // stride of the per-stage trig cache (8 words used; the long horizons have no LDS to spare for the padding)
-    static constexpr int TRGS = N >= MMPC_SLIM_NMIN ? 8 : MMPC_TRGS;
+    // stride of the per-stage trig cache (8 words used): with 8 the stage lanes' words sit 16 dwords apart - two LDS banks for 21 lanes;
+    // the long horizons have no LDS to spare for the padding
+    static constexpr int TRGS = N >= MMPC_SLIM_NMIN ? 8 : 9;
     static constexpr int NPASS = PADMAP ? (N * 16 + MMPC_WAVE - 1) / MMPC_WAVE : (NPAIR + MMPC_WAVE - 1) / MMPC_WAVE;
     // Riccati recursion on 16x16 MFMA tiles in homogeneous form: tile index t < NX is state t, t = NX the constant 1 (its
     // row and column carry the gradient), NX < t <= NV input t-NX-1.  K-blocks (4 rows each) that cover the (x, 1) rows /
@@ -206,11 +207,6 @@ struct MmpcFastLayout {
 // per-instance block of global memory (L2 / MALL resident): the Riccati legs only store them, the back-substitution is one
 // batched load / store pass and the roll-out fetches its gain row ahead of the chain.  At N = 30, M = 8 that is 52.6 -> 40.6 KB
 // of LDS per problem: four resident problems per CU - one per SIMD - instead of three.
-#ifndef MMPC_GK_MASK
-#define MMPC_GK_MASK 0   // gain block: 1 = lanes without an entry of a pivot row do not store, 0 = they store to a dump slot of the block as the
-                         // LDS variant does (measured on C5: the masked store - exec handling on the chain of every leg - 300 k against 314 k solves/s,
-                         // for 10 % less write traffic out of L2)
-#endif
 #ifndef MMPC_GAINS_GLOBAL_NMIN
 #define MMPC_GAINS_GLOBAL_NMIN MMPC_SLIM_NMIN
 #endif
@@ -298,7 +294,6 @@ struct MmpcLaneState {
 };
 
 #ifndef MMPC_EMU
-#if MMPC_RED_DPP
 MMPC_DEV double mmpc_op_add(double a, double b) { return a + b; }
 MMPC_WAVE_RED(mmpc_wave_sum, mmpc_op_add)
 MMPC_WAVE_RED(mmpc_wave_max, mmpc_vmax)
@@ -307,30 +302,9 @@ MMPC_WAVE_RED4(mmpc_wave_sum4, mmpc_op_add)
 MMPC_WAVE_RED4(mmpc_wave_max4, mmpc_vmax)
 #define MMPC_RED4_SUM(i0, i1, i2, i3, out) mmpc_wave_sum4(wr_one[i0], wr_one[i1], wr_one[i2], wr_one[i3], out)
 #define MMPC_RED4_MAX(i0, i1, i2, i3, out) mmpc_wave_max4(wr_one[i0], wr_one[i1], wr_one[i2], wr_one[i3], out)
-#else
-MMPC_DEV double mmpc_wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-MMPC_DEV double mmpc_wave_max(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = mmpc_vmax(v, __shfl_xor(v, o));
-    return v;
-}
-MMPC_DEV double mmpc_wave_min(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = mmpc_vmin(v, __shfl_xor(v, o));
-    return v;
-}
-#endif
 #define MMPC_RED_SUM(i) mmpc_wave_sum(wr_one[i])
 #define MMPC_RED_MAX(i) mmpc_wave_max(wr_one[i])
 #define MMPC_RED_MIN(i) mmpc_wave_min(wr_one[i])
-#if !MMPC_RED_DPP
-#define MMPC_RED4_SUM(i0, i1, i2, i3, out) { (out)[0] = MMPC_RED_SUM(i0); (out)[1] = MMPC_RED_SUM(i1); (out)[2] = MMPC_RED_SUM(i2); (out)[3] = MMPC_RED_SUM(i3); }
-#define MMPC_RED4_MAX(i0, i1, i2, i3, out) { (out)[0] = MMPC_RED_MAX(i0); (out)[1] = MMPC_RED_MAX(i1); (out)[2] = MMPC_RED_MAX(i2); (out)[3] = MMPC_RED_MAX(i3); }
-#endif
 #else
 // host emulation: butterfly in the same pairing order as the device shuffles, so that the
 // floating-point sums are bit-identical on every "lane"
@@ -338,10 +312,10 @@ static inline double mmpc_emu_red(double (*wr)[9], int i, int op) {
     double v[MMPC_WAVE], w[MMPC_WAVE];
     for (int l = 0; l < MMPC_WAVE; l++) v[l] = wr[l][i];
     for (int q = 0; q < 6; q++) {
-        const int o = MMPC_RED_DPP ? (1 << q) : (32 >> q);
+        const int o = 1 << q;
         for (int l = 0; l < MMPC_WAVE; l++) {
-            // partner of the device butterfly: lane ^ 1, ^ 2, the mirror inside 8 / 16 lanes, lane ^ 16, ^ 32  (ds_bpermute form: lane ^ o)
-            const int p = !MMPC_RED_DPP ? (l ^ o) : (o == 4 ? ((l & ~7) | (7 - (l & 7))) : (o == 8 ? ((l & ~15) | (15 - (l & 15))) : (l ^ o)));
+            // partner of the device butterfly: lane ^ 1, ^ 2, the mirror inside 8 / 16 lanes, lane ^ 16, ^ 32
+            const int p = o == 4 ? ((l & ~7) | (7 - (l & 7))) : (o == 8 ? ((l & ~15) | (15 - (l & 15))) : (l ^ o));
             const double a = v[l], b = v[p];
             w[l] = op == 0 ? a + b : (op == 1 ? (a > b ? a : b) : (a < b ? a : b));
         }
@@ -355,7 +329,6 @@ static inline double mmpc_emu_red(double (*wr)[9], int i, int op) {
 // the four-at-a-time reductions of the device (MMPC_WAVE_RED4): lane l with l + 32, the result with its neighbour 16 lanes on, then the
 // in-row butterfly of mmpc_emu_red over 16 lanes
 static inline double mmpc_emu_red4(double (*wr)[9], int i, int op) {
-    if (!MMPC_RED_DPP) return mmpc_emu_red(wr, i, op);
     double v[16], w[16];
     for (int l = 0; l < 16; l++) {
         const double a0 = wr[l][i], a1 = wr[l + 16][i], a2 = wr[l + 32][i], a3 = wr[l + 48][i];
@@ -431,11 +404,7 @@ MMPC_DEV void mmpc_solve_fast(const MmpcParams &P, const MmpcIO io, double *lds 
 #define MMPC_ROW_LANE const int rs = RG > 1 ? lane / NS : 0, rk = lane - rs * NS; const bool rlane = M > 0 && lane < RG * NS;
     // stages per trip of the Riccati / forward loops: unrolling saves the per-stage pointer bumps and register shuffles,
     // but costs registers - it only pays where the kernel does not spill (measured per instantiation)
-#ifdef MMPC_UNROLL_BASE
-    constexpr bool ROOMY = N <= MMPC_UNROLL_NMAX;
-#else
     constexpr bool ROOMY = KIND == 0 && N <= MMPC_UNROLL_NMAX;
-#endif
     constexpr bool SLIM = N >= MMPC_SLIM_NMIN;   // references and per-stage obstacles are read from HBM/L2 (see mmpc_fast_layout)
     constexpr int RIC_UNROLL = ROOMY ? MMPC_RIC_UNROLL : 1, FWD_UNROLL = ROOMY ? (MMPC_FWD_UNROLL < N ? MMPC_FWD_UNROLL : N) : 1;
     const MmpcFastLayout L = mmpc_fast_layout<KIND, N>(M, ops);
@@ -670,7 +639,6 @@ MMPC_DEV void mmpc_solve_fast(const MmpcParams &P, const MmpcIO io, double *lds 
     MMPC_PAIR_SETUP
 #pragma unroll
     for (int p = 0; p < NPASS; p++) {
-        MMPC_SFENCE(0)
         MMPC_PAIR(p)
         ls.lo_z[p] = 0.0; ls.hi_z[p] = 0.0; ls.b_lo[p] = -1e300; ls.b_hi[p] = 1e300;
         if (pok) {
@@ -810,7 +778,6 @@ MMPC_DEV void mmpc_solve_fast(const MmpcParams &P, const MmpcIO io, double *lds 
         MMPC_PAIR_SETUP
 #pragma unroll
         for (int p = 0; p < NPASS; p++) {
-            MMPC_SFENCE(1)
             MMPC_PAIR(p)
             if (pok) {
                 const double val = XU[idx], dv = DXU[idx], vn = val + d_alpha * dv;

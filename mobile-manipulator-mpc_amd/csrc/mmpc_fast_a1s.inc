@@ -25,7 +25,6 @@
 #pragma unroll
                     for (int a = 0; a < 3; a++) { dr[a] = TRG[MMPC_MUL24(k, F::TRGS) + 2 + a]; dz[a] = TRG[MMPC_MUL24(k, F::TRGS) + 5 + a]; }
                 }
-                MMPC_SFENCE(9)
 #pragma unroll
                 for (int e = 0; e < NXX; e++) hxx[e] = 0.0;
 #pragma unroll

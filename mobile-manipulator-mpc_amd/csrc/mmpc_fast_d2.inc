@@ -89,7 +89,6 @@
         MMPC_PAIR_SETUP
 #pragma unroll
         for (int p = 0; p < NPASS; p++) {
-            MMPC_SFENCE(10)
             MMPC_PAIR(p)
             if (pok) {
                 const double lo = ls.b_lo[p], hi = ls.b_hi[p];

@@ -66,7 +66,6 @@
                 for (int m = 0; m < M; m++) { const double *o = obs_ptr(k, m); ob[3 * m] = o[0]; ob[3 * m + 1] = o[1]; ob[3 * m + 2] = o[2]; }
             }
             const double sk = S[k], sks_ld = S[slack_idx(k)];
-            MMPC_SFENCE(2)
             double sn, cs;
             mmpc_sincos(xk[2], &sn, &cs);
             double *cv = CV + MMPC_MUL24(k, MMPC_NCV);
@@ -163,7 +162,7 @@
         double e_d = 0.0, e_p = MMPC_WR(1), tzmax = MMPC_WR(2), tzmin = MMPC_WR(3), zsum = MMPC_WR(4), phi = MMPC_WR(5), th = MMPC_WR(6);
         MmpcLogAcc la; la.init();
         // long horizons read the references and the previous inputs from HBM / L2: the loads of ALL passes ahead of the loop (one
-        // exposed round trip instead of one per pass - the scheduler fences below keep the compiler from doing that itself)
+        // exposed round trip instead of one per pass)
         double g_ref[SLIM ? NPASS : 1], g_ul[SLIM ? NPASS : 1];
         static_assert(!(SLIM && F::PADMAP), "the padded pair map is not written for the slim layout");
         if (SLIM) {
@@ -186,7 +185,6 @@
         (void)pul_b; (void)pul_s; (void)pau_; (void)pwq_b; (void)pwq_s;
 #pragma unroll
         for (int p = 0; p < NPASS; p++) {
-            MMPC_SFENCE(3)
             MMPC_PAIR(p)
             if (pok) {
                 MMPC_PAIR_KV(p)
@@ -199,7 +197,6 @@
                 const double val = XU[idx], ref = SLIM ? g_ref[SLIM ? p : 0] : ref_at(idx, k, v), rb0 = RB[idx];
                 const double ul = SLIM ? g_ul[SLIM ? p : 0] : (F::PADMAP ? ULAST[pul_b + p * pul_s] : ulast_at(isu ? k : 0, au)), ww0 = CST[MMPC_C_WW + au];
                 const double wq = CST[F::PADMAP ? pwq_b + p * pwq_s : (v < NX ? (k < N ? MMPC_C_WQ : MMPC_C_WP) + v : MMPC_C_WR + v - NX)];
-                MMPC_SFENCE(4)
                 // cost gradient / value (diagonal weights): mpc_wholebody_qref.py:192-201,240-242
                 double e = val - ref;
                 if (KIND == 1 && v == 2) e = mmpc_angle_diff(val, ref);
@@ -371,11 +368,7 @@
             // (always true.  Kept a run-time value on purpose: as a compile-time constant the curvature terms of the circle rows
             //  join the basic blocks around them, the scheduler moves their loads up and the kernel spills 76 instead of 44
             //  vector registers - the branch the old Hessian ladder needed is the cheaper of the two)
-#ifdef MMPC_EXACT_CONST   // (A/B switch of the note above)
-            constexpr bool exact = true;
-#else
             const bool exact = P.max_iter >= 0;
-#endif
             constexpr bool dyn_curv = true;
             const double reg = prox + dw;
             int ric_bad = 0;   // a pivot of this pass was not positive (every lane factorises the same matrix: uniform)
@@ -424,7 +417,6 @@
             (void)phd_b; (void)phd_s;
 #pragma unroll
             for (int p = 0; p < NPASS; p++) {
-                MMPC_SFENCE(5)
                 MMPC_PAIR(p)
                 if (pok) {
                     MMPC_PAIR_KV(p)
@@ -434,7 +426,6 @@
                     double *hd = F::PADMAP ? lds + (phd_b + p * phd_s + (pt_ ? 8 * p * p + 6 * p : 0))
                                            : (v < NX ? HXX + k * NXX + v * (v + 1) / 2 + v : HUUD + (k < N ? k : 0) * NU + v - NX);
                     const double val = XU[idx], q0 = QXU[idx], h0 = *hd;
-                    MMPC_SFENCE(6)
                     double wsum = 0.0, gsum = 0.0;
                     if (alo) { const double it_ = mmpc_rcp(mmpc_box_t(val - lo)); wsum += ls.lo_z[p] * it_; gsum -= mu * it_; }
                     if (ahi) { const double it_ = mmpc_rcp(mmpc_box_t(hi - val)); wsum += ls.hi_z[p] * it_; gsum += mu * it_; }
@@ -471,9 +462,6 @@
                 MMPC_MFMA(rM, ls.rAB[0], ls.rT[0])
                 MMPC_MFMA(rM, ls.rAB[1], ls.rT[1])
                 if (NKB > 2) MMPC_MFMA(rM, ls.rAB[NKB > 2 ? 2 : 0], ls.rT[NKB > 2 ? 2 : 0])
-#if defined(MMPC_EXP) && MMPC_EXP == 3 && !defined(MMPC_EMU)
-                { const double zero_ = 0.0; ls_one.rM = __builtin_amdgcn_mfma_f64_16x16x4f64(zero_, ls_one.rAB[0], ls_one.rM, 0, 0, 0); }
-#endif
                 MMPC_TSF(6)
 #define MMPC_NEXT_OPERANDS                                                                                                         \
                 LANES_BEGIN_NL                                                                                                             \
@@ -522,18 +510,6 @@
                         // refinement in a row; the determinant's rounding, eps d0 d11 against d0 d1, is that of the sequential d1)
                         const double det = fma(-d01, d01, d00 * d11), n1 = -(d00 * ls.mg[ga + 1]);
                         double i0 = mmpc_rcp_piv(d00), rdet = mmpc_rcp_piv(det);
-#if defined(MMPC_EXP) && !defined(MMPC_EMU)   // (timing experiments: what a stage is bound by)
-#if MMPC_EXP == 1      // four dependent identity fma on both reciprocals' chains
-                        asm volatile("v_fma_f64 %0, %0, 1.0, 0\n v_fma_f64 %0, %0, 1.0, 0\n v_fma_f64 %0, %0, 1.0, 0\n v_fma_f64 %0, %0, 1.0, 0" : "+v"(i0));
-                        asm volatile("v_fma_f64 %0, %0, 1.0, 0\n v_fma_f64 %0, %0, 1.0, 0\n v_fma_f64 %0, %0, 1.0, 0\n v_fma_f64 %0, %0, 1.0, 0" : "+v"(rdet));
-#elif MMPC_EXP == 2    // eight independent 32-bit VALU instructions
-                        { int dm_ = 1; asm volatile("v_mov_b32 %0, %0\n v_mov_b32 %0, %0\n v_mov_b32 %0, %0\n v_mov_b32 %0, %0\n v_mov_b32 %0, %0\n v_mov_b32 %0, %0\n v_mov_b32 %0, %0\n v_mov_b32 %0, %0" : "+v"(dm_)); }
-#elif MMPC_EXP == 7    // eight scalar instructions
-                        { int sm_; asm volatile("s_mov_b32 %0, 1\n s_add_u32 %0, %0, 1\n s_add_u32 %0, %0, 1\n s_add_u32 %0, %0, 1\n s_add_u32 %0, %0, 1\n s_add_u32 %0, %0, 1\n s_add_u32 %0, %0, 1\n s_add_u32 %0, %0, 1" : "=s"(sm_) : : "scc"); }
-#elif MMPC_EXP == 4    // eight independent f64 VALU instructions
-                        { double dm_ = c; asm volatile("v_fma_f64 %0, %1, 1.0, 0\n v_fma_f64 %0, %1, 1.0, 0\n v_fma_f64 %0, %1, 1.0, 0\n v_fma_f64 %0, %1, 1.0, 0\n v_fma_f64 %0, %1, 1.0, 0\n v_fma_f64 %0, %1, 1.0, 0\n v_fma_f64 %0, %1, 1.0, 0\n v_fma_f64 %0, %1, 1.0, 0" : "=&v"(dm_) : "v"(c)); }
-#endif
-#endif
                         const double l = d01 * i0;
                         const double cb = fma(-l * ls.mg[ga + 1], co, c);
                         const double wn = cb * fma(rdet, n1, -(i0 * ls.mg[ga]));
@@ -554,21 +530,16 @@
                         ls.pv0 = d; ls.pv1 = d;
                     }
                     LANES_END_REG
-                    MMPC_SFENCE(7)
                     MMPC_MFMA(rM, ls.opa, ls.opb)
                     // operands of the next stage travel while this one eliminates its inputs: issued behind the first leg's product
                     if (leg == 0) { MMPC_NEXT_OPERANDS }
                     LANES_BEGIN_NL
                     auto &ls = MMPC_LS;
-#if defined(MMPC_EXP) && (MMPC_EXP == 5 || MMPC_EXP == 6) && !defined(MMPC_EMU)   // eight independent f64 (5) / 32-bit (6) VALU instructions in the product's shadow
-                    { double dm_ = ls.pv0; int di_ = 1;
-                      if (MMPC_EXP == 5) asm volatile("v_fma_f64 %0, %1, 1.0, 0\n v_fma_f64 %0, %1, 1.0, 0\n v_fma_f64 %0, %1, 1.0, 0\n v_fma_f64 %0, %1, 1.0, 0\n v_fma_f64 %0, %1, 1.0, 0\n v_fma_f64 %0, %1, 1.0, 0\n v_fma_f64 %0, %1, 1.0, 0\n v_fma_f64 %0, %1, 1.0, 0" : "=&v"(dm_) : "v"(ls.pv1));
-                      else asm volatile("v_mov_b32 %0, %0\n v_mov_b32 %0, %0\n v_mov_b32 %0, %0\n v_mov_b32 %0, %0\n v_mov_b32 %0, %0\n v_mov_b32 %0, %0\n v_mov_b32 %0, %0\n v_mov_b32 %0, %0" : "+v"(di_)); }
-#endif
                     if (!(ls.pv0 > 0.0 && ls.pv1 > 0.0)) ric_bad = 1;   // (NaN fails too) the pass stops at the next stage and is redone with a (larger) inertia correction
-                    // (lanes that hold no entry of the row write to their dump slot - no branch; MMPC_GK_MASK: masked instead, see there)
-                    if (!(GK && MMPC_GK_MASK) || ls.kl_s[leg] != 0)
-                        *(double *)((char *)KBASE + (unsigned)(ls.kl_b[leg] + MMPC_MUL24(k, ls.kl_s[leg]))) = ls.opa;   // (-w: see the gains below)
+                    // (lanes that hold no entry of the row write to their dump slot - no branch; in the gain block of the long horizons a
+                    //  masked store - exec handling on the chain of every leg - measured 300 k against 314 k solves/s on C5, for 10 % less
+                    //  write traffic out of L2)
+                    *(double *)((char *)KBASE + (unsigned)(ls.kl_b[leg] + MMPC_MUL24(k, ls.kl_s[leg]))) = ls.opa;   // (-w: see the gains below)
                     LANES_END_REG
                 }
 #undef MMPC_NEXT_OPERANDS
@@ -607,7 +578,10 @@
         // ---- gains of all stages from the normalised pivot rows, by back-substitution over the inputs (the last eliminated
         //      input depends on x only): K_a = -(w_a[x,1] + sum_{b>a} w_a[u_b] K_b), in place, one lane per (stage, column).  The legs
         //      stored s = -w (the product's operand as it stands): K_a = s_a[x,1] + sum_{b>a} s_a[u_b] K_b - the same bits, no negations
-        if (GK) MMPC_GFENCE();   // the legs' stores to the gain block are read by other lanes
+        // (Long horizons: the legs' stores to the gain block in global memory are read here by other lanes of the SAME wave.  The vector
+        //  memory instructions of a wavefront are issued and processed in order, so the wavefront-scope fence of LANES_END (compiler
+        //  ordering only, no s_waitcnt) is all that is needed, here and after the back-substitution - waiting for the stores'
+        //  acknowledgement with a workgroup-scope fence cost 2 x ~1 k cycles per iteration.)
         LANES_BEGIN
         if constexpr (!GK && NX + 1 <= 16) {
             // gains in LDS: a row of 16 lanes takes one stage per trip, the lane's column is the column of [K_k | kf_k] (stage 4 t + lane / 16,
@@ -690,7 +664,6 @@
             }
         }
         LANES_END
-        if (GK) MMPC_GFENCE();
         MMPC_TS(8)
         // ---- forward roll-out: lane i < NX carries dx_k[i] in a register; a stage broadcasts the NX values through scalar
         //      registers (v_readlane), forms the input step of its row and the next dx - no LDS round trip on the chain.
@@ -790,7 +763,7 @@
                 }
 #endif
                 double dx[NX];
-#if !defined(MMPC_EMU) && MMPC_FWD_DPP
+#ifndef MMPC_EMU
                 // (the rows of the dynamics sit in lanes 0 .. NX-1, all in the first row of 16 lanes: dx_k[j] by a row broadcast; the
                 //  other rows of the wave broadcast their own lanes' don't-care values and store to their dump slots)
                 static_assert(NX <= 16, "the roll-out's row lanes must share a row of 16 lanes");
@@ -836,7 +809,6 @@
             for (int j = 0; j < NX; j++) { dx[j] = DXU[MMPC_MUL24(k, NV) + j]; y[j] = QXU[MMPC_MUL24(k, NV) + j] + LAM[MMPC_MUL24(k, NX) + j]; }
 #pragma unroll
             for (int e = 0; e < NXX; e++) pk[e] = HXX[MMPC_MUL24(k, NXX) + e];
-            MMPC_SFENCE(8)
 #pragma unroll
             for (int i = 0; i < NX; i++) {
 #pragma unroll

@@ -35,7 +35,6 @@ MMPC_DEV double mmpc_rcp3(double x) { return 1.0 / x; }
 MMPC_DEV double mmpc_rcp_piv(double x) { return 1.0 / x; }
 MMPC_DEV float mmpc_log2f_raw(float x) { return log2f(x); }
 MMPC_DEV float mmpc_exp2f_raw(float x) { return exp2f(x); }
-MMPC_DEV void mmpc_sched_fence() {}
 #else
 // v_rcp_f64 / v_rsq_f64 + one cubic step, in three / five dependent operations; the IEEE division / sqrt sequences are ~3x longer.
 // Worst relative error, exact rational arithmetic over [1e-30, 1e30] and the mantissa edges (tests/test_gpu_primitives.py, MI355X):
@@ -84,12 +83,6 @@ MMPC_DEV double mmpc_rsqrt(double x) {
 }
 MMPC_DEV float mmpc_log2f_raw(float x) { return __builtin_amdgcn_logf(x); }     // v_log_f32 / v_exp_f32: no subnormals in or out
 MMPC_DEV float mmpc_exp2f_raw(float x) { return __builtin_amdgcn_exp2f(x); }
-// keeps the scheduler from interleaving independent unrolled bodies (bounds the live registers)
-#ifdef MMPC_NO_SCHED_FENCE
-MMPC_DEV void mmpc_sched_fence() {}
-#else
-MMPC_DEV void mmpc_sched_fence() { __builtin_amdgcn_sched_barrier(0); }
-#endif
 #endif
 
 // x^e for x >= 0 with a single-precision logarithm and exponential (only used by the filter's switching rule, a heuristic threshold:
@@ -188,12 +181,6 @@ MMPC_DEV double mmpc_lower16_f64(double v) {
 // asserted on the device, every lane of every reduction against the stand-in's bits (tests/test_gpu_primitives.py).  A NaN:
 // v_max_f64 / v_min_f64 drop it (the maximum of the other 63 lanes comes back in every lane), the stand-in's ternary keeps or
 // drops it by position; the sums return NaN in both builds.
-#endif
-#ifndef MMPC_RED_DPP
-#define MMPC_RED_DPP 1   // wave reductions through DPP / permlane swaps (steps 1..32) instead of ds_bpermute butterflies (steps 32..1)
-#endif
-#ifndef MMPC_EMU
-#if MMPC_RED_DPP
 template <int CTRL>
 MMPC_DEV double mmpc_dpp_f64(double v) {
     const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, 0xf, 0xf, true);
@@ -243,7 +230,6 @@ MMPC_DEV void NAME(double a, double b, double c, double d, double *out) {       
     out[0] = mmpc_readlane_f64(v, 0); out[2] = mmpc_readlane_f64(v, 16);                                      \
     out[1] = mmpc_readlane_f64(v, 32); out[3] = mmpc_readlane_f64(v, 48); }
 #endif
-#endif
 
 // the same butterfly over an array of MMPC_WAVE per-lane partials in LDS (the generic kernel's reductions): device - every lane
 // takes its own word and all end with the same bits; host - the same pairing order.  OP: 0 sum, 1 max, 2 min, 3 the running
@@ -253,9 +239,9 @@ static inline double mmpc_emu_red_arr(const double *a, int op) {
     double v[MMPC_WAVE], w[MMPC_WAVE];
     for (int l = 0; l < MMPC_WAVE; l++) v[l] = a[l];
     for (int q = 0; q < 6; q++) {
-        const int o = MMPC_RED_DPP ? (1 << q) : (32 >> q);
+        const int o = 1 << q;
         for (int l = 0; l < MMPC_WAVE; l++) {
-            const int p = !MMPC_RED_DPP ? (l ^ o) : (o == 4 ? ((l & ~7) | (7 - (l & 7))) : (o == 8 ? ((l & ~15) | (15 - (l & 15))) : (l ^ o)));
+            const int p = o == 4 ? ((l & ~7) | (7 - (l & 7))) : (o == 8 ? ((l & ~15) | (15 - (l & 15))) : (l ^ o));
             const double x = v[l], y = v[p];
             w[l] = op == 0 ? x + y : (op == 1 ? (x > y ? x : y) : (op == 2 ? (x < y ? x : y) : ((x > y || x != x) ? x : y)));
         }
