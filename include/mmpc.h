@@ -188,6 +188,33 @@ int mmpc_resume_batch_device(mmpc_handle h, int B, const double *d_x_init, const
                              double *d_s, int *d_status, int *d_iters, double *d_cost, double *d_err, void *stream);
 int mmpc_suspended_count(mmpc_handle h, int *count);
 
+/* The glue of one receding-horizon tick for B robots that stay in device memory between ticks (no reference counterpart as
+ * a batch; per robot it is the reference's closed loop without the simulator, interface_wholebody_qref.py:100-143).  Whole-body
+ * handles created with obs_per_stage = 1 only (MMPC_E_UNSUPPORTED otherwise); N, M, dt and xlim come from the handle.  One
+ * launch, one 64-lane workgroup per robot b:
+ *   1. advance - skipped when d_U_prev is NULL (before the first tick): x_b <- f(clip(x_b, xlim), U_prev[b][0]) with the plant
+ *      step of robot_models/mobile_manipulator.py (every operation rounded on its own, no fused multiply-add), tick_b <- tick_b + 1;
+ *   2. d_x_in[b][9] = clip(x_b, xlim): the x_init of the solve;
+ *   3. j = the row of the robot's global plan d_glob[b][nglob][9] nearest to the (unclipped) x_b in columns 0, 1 - the first row
+ *      that attains the minimum of sqrt(dx dx + dy dy) (calcLocalRefTraj, :353-396); a robot whose state is not finite takes
+ *      j = 0 and its NaN reaches the solve, which reports MMPC_STATUS_NUMERIC for it alone;
+ *   4. d_traj_ref[b][k] = glob[b][min(j + k, nglob - 1)], k = 0..N; d_start[b] = j (int32);
+ *   5. d_obs[b][k][m] = (c_x + v_x t_k, c_y + v_y t_k, r), t_k = (double)(tick_b + k) dt, from d_obs0[B][M][3] = (c_x, c_y, r) and
+ *      d_vel[B][M][2];
+ *   6. shifted warm start - only when d_U_prev, d_u_guess and d_x_guess are all given: u_guess[k] = U_prev[k + 1] for k < N - 1,
+ *      u_guess[N - 1] = U_prev[N - 1]; x_guess[0] = x_in, x_guess[k + 1] = f(x_guess[k], u_guess[k]): the initial point that
+ *      mmpc_set_warm_start describes (register d_u_guess there, pass d_x_guess to the solve).  d_u_guess must not be d_U_prev.
+ * d_x [B][9] and d_tick [B] (int64) are updated in place and are required (d_tick: when the call advances or writes d_obs).
+ * Every output pointer may be NULL and that part is skipped: with d_x, d_tick and d_U_prev alone the call is the plain plant
+ * step after the last tick.  The window and the start index need d_glob (nglob >= 1), the table d_obs0 and d_vel; a missing
+ * one, or B > max_batch, is MMPC_E_ARG.  B = 0 is a no-op.  Asynchronous on `stream` and ordered against the handle's other
+ * launches as they are among themselves; no allocation, copy or synchronisation inside.  A tick of the loop is: this call
+ * with the previous tick's d_U as d_U_prev, mmpc_solve_batch_device on its outputs (d_u_last = the same previous d_U) into the
+ * other of two output sets, swap. */
+int mmpc_tick_prepare_device(mmpc_handle h, int B, double *d_x, long long *d_tick, const double *d_U_prev, const double *d_glob,
+                             int nglob, const double *d_obs0, const double *d_vel, double *d_x_in, double *d_traj_ref, int *d_start,
+                             double *d_obs, double *d_u_guess, double *d_x_guess, void *stream);
+
 /* Streams and threads: a handle owns device state that its launches read and write (parameter block, schedule hint,
  * warm start).  Calls on one handle must come from one host thread at a time.  Launches may use different streams:
  * a launch on another stream than the handle's previous one is ordered after it (event wait), and the entry points

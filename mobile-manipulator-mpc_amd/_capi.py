@@ -23,7 +23,8 @@ class MmpcConfig(C.Structure):
 
 EXPORTS = ["mmpc_create", "mmpc_destroy", "mmpc_set_weights", "mmpc_set_terminal_xy_equality", "mmpc_reset",
            "mmpc_solve_batch", "mmpc_solve_batch_device", "mmpc_get_u_latest", "mmpc_set_u_latest",
-           "mmpc_lds_bytes", "mmpc_problems_per_cu", "mmpc_set_warm_start", "mmpc_set_schedule_hint", "mmpc_set_iteration_budget", "mmpc_resume_batch_device", "mmpc_solve_list_device", "mmpc_suspended_count", "mmpc_last_error", "mmpc_version", "mmpc_ik_batch", "mmpc_ik_batch_device"]
+           "mmpc_lds_bytes", "mmpc_problems_per_cu", "mmpc_set_warm_start", "mmpc_set_schedule_hint", "mmpc_set_iteration_budget", "mmpc_resume_batch_device", "mmpc_solve_list_device", "mmpc_suspended_count", "mmpc_last_error", "mmpc_version", "mmpc_ik_batch", "mmpc_ik_batch_device",
+           "mmpc_tick_prepare_device"]
 
 _lib = None
 _dp = C.POINTER(C.c_double)
@@ -68,6 +69,7 @@ def lib():
         L.mmpc_version.restype = C.c_char_p
         L.mmpc_ik_batch.argtypes = [C.c_int, C.c_int, _dp, _dp, _dp, _ip, _ip]
         L.mmpc_ik_batch_device.argtypes = [C.c_int, C.c_int] + [C.c_void_p] * 5 + [C.c_void_p]
+        L.mmpc_tick_prepare_device.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 8 + [C.c_void_p]
         _lib = L
     return _lib
 
@@ -290,3 +292,32 @@ class Engine:
         """mmpc_resume_batch_device: continues the instances the preceding budgeted solve_batch_device call (same tensors,
         same `out`) left suspended; the other rows of `out` are not touched."""
         return self.solve_batch_device(x_init, traj_ref, u_ref, u_last, obs, x_guess=x_guess, out=out, stream=stream, resume=True)
+
+    def tick_prepare(self, x, tick, U_prev=None, glob=None, obs0=None, vel=None, x_in=None, traj_ref=None, start=None, obs=None,
+                     u_guess=None, x_guess=None, stream=None):
+        """mmpc_tick_prepare_device: the glue of one receding-horizon tick in one launch, asynchronous on torch's current stream
+        (or `stream`).  x (B,9) float64 and tick (B,) int64 are updated in place (advanced with U_prev[:, 0] when U_prev is given);
+        every other tensor is optional: glob (B,nglob,9), obs0 (B,M,3), vel (B,M,2) in; x_in (B,9), traj_ref (B,N+1,9), start (B,)
+        int32, obs (B,N+1,M,3), u_guess (B,N,5), x_guess (B,N+1,9) out.  Contiguous cuda tensors on one device."""
+        import torch
+        N, M = self.N, self.M
+        B = x.shape[0]
+        dev = x.device
+        ng = glob.shape[1] if glob is not None and glob.dim() == 3 else 0
+        f64, i64, i32 = torch.float64, torch.int64, torch.int32
+        for name, t_, shp, dt_ in (("x", x, (B, 9), f64), ("tick", tick, (B,), i64), ("U_prev", U_prev, (B, N, 5), f64), ("glob", glob, (B, ng, 9), f64),
+                                   ("obs0", obs0, (B, M, 3), f64), ("vel", vel, (B, M, 2), f64), ("x_in", x_in, (B, 9), f64),
+                                   ("traj_ref", traj_ref, (B, N + 1, 9), f64), ("start", start, (B,), i32), ("obs", obs, (B, N + 1, M, 3), f64),
+                                   ("u_guess", u_guess, (B, N, 5), f64), ("x_guess", x_guess, (B, N + 1, 9), f64)):
+            if t_ is None:
+                if name in ("x", "tick"):
+                    raise ValueError("%s is required" % name)
+                continue
+            if tuple(t_.shape) != shp or t_.dtype != dt_ or not t_.is_cuda or not t_.is_contiguous() or t_.device != dev:
+                raise ValueError("%s must be a contiguous %s tensor of shape %s on %s" % (name, dt_, shp, dev))
+        if u_guess is not None and U_prev is not None and u_guess.data_ptr() == U_prev.data_ptr():
+            raise ValueError("u_guess must not be U_prev")
+        st = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
+        p = lambda t_: C.c_void_p(t_.data_ptr()) if t_ is not None else None
+        self._chk(lib().mmpc_tick_prepare_device(self._h, B, p(x), p(tick), p(U_prev), p(glob), int(ng), p(obs0), p(vel), p(x_in), p(traj_ref),
+                                                 p(start), p(obs), p(u_guess), p(x_guess), C.c_void_p(st)), "mmpc_tick_prepare_device")

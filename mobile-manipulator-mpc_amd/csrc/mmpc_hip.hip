@@ -12,6 +12,7 @@
 #include "mmpc_core.h"
 #include "mmpc_fast.h"
 #include "mmpc_ik.h"
+#include "mmpc_tick.h"
 
 template <int KIND, int NC = 0, int MC = -1, int OPSC = -1, int LC = -1>
 __global__ __launch_bounds__(MMPC_WAVE) void mmpc_solve_kernel(
@@ -826,4 +827,43 @@ extern "C" int mmpc_ik_batch(int device, int B, const double *q0, const double *
     if (e != hipSuccess) { snprintf(g_err, sizeof(g_err), "mmpc_ik_batch: %s", hipGetErrorString(e)); rc = MMPC_E_HIP; }
     (void)hipFree(d_q0); (void)hipFree(d_t); (void)hipFree(d_q); (void)hipFree(d_st); (void)hipFree(d_it);
     return rc;
+}
+
+// ---- the glue of a receding-horizon tick (mmpc_tick.h): one workgroup per robot, whole-body kind with a per-stage obstacle table
+__global__ __launch_bounds__(MMPC_WAVE) void mmpc_tick_kernel(
+    const MmpcParams *__restrict__ Pp, int B, double *__restrict__ x, long long *__restrict__ tick, const double *__restrict__ U_prev,
+    const double *__restrict__ glob, int nglob, const double *__restrict__ obs0, const double *__restrict__ vel,
+    double *__restrict__ x_in, double *__restrict__ traj_ref, int *__restrict__ start, double *__restrict__ obs,
+    double *__restrict__ u_guess, double *__restrict__ x_guess) {
+    __shared__ double lds[MMPC_TICK_LDS];
+    const int b = (int)blockIdx.x;
+    if (b >= B) return;
+    mmpc_tick_robot(*Pp, b, x, tick, U_prev, glob, nglob, obs0, vel, x_in, traj_ref, start, obs, u_guess, x_guess, lds);
+}
+
+extern "C" int mmpc_tick_prepare_device(mmpc_handle h, int B, double *d_x, long long *d_tick, const double *d_U_prev,
+                                        const double *d_glob, int nglob, const double *d_obs0, const double *d_vel, double *d_x_in,
+                                        double *d_traj_ref, int *d_start, double *d_obs, double *d_u_guess, double *d_x_guess,
+                                        void *stream) {
+    if (!h) return MMPC_E_ARG;
+    if (h->cfg.kind != MMPC_KIND_WHOLEBODY || !h->hp.obs_per_stage)
+        return fail(h, MMPC_E_UNSUPPORTED, "mmpc_tick_prepare_device: %s%s", "needs a whole-body handle (joint-space reference) created with obs_per_stage = 1");
+    if (B == 0) return MMPC_OK;
+    if (B < 1 || B > h->cfg.max_batch) return fail(h, MMPC_E_ARG, "mmpc_tick_prepare_device: %s%s", "B must be in 0..max_batch");
+    if (!d_x) return fail(h, MMPC_E_ARG, "mmpc_tick_prepare_device: %s%s", "d_x is required");
+    if (!d_tick && (d_U_prev || d_obs)) return fail(h, MMPC_E_ARG, "mmpc_tick_prepare_device: %s%s", "the advance and the obstacle table need d_tick");
+    if ((d_traj_ref || d_start) && !d_glob) return fail(h, MMPC_E_ARG, "mmpc_tick_prepare_device: %s%s", "the window and the start index need d_glob");
+    if (d_glob && (nglob < 1 || nglob > (1 << 24))) return fail(h, MMPC_E_ARG, "mmpc_tick_prepare_device: %s%s", "nglob must be in 1..2^24");
+    if (d_obs && h->cfg.M > 0 && (!d_obs0 || !d_vel)) return fail(h, MMPC_E_ARG, "mmpc_tick_prepare_device: %s%s", "the obstacle table needs d_obs0 and d_vel");
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    hipStream_t st = (hipStream_t)stream;
+    // ordered against the handle's launches as they are among themselves: the solve reads what this writes (and the registered
+    // u_guess), the next call of this reads the solve's U
+    if (h->ev_valid && st != h->last_stream) HIPCHK(h, hipStreamWaitEvent(st, h->ev, 0));
+    hipLaunchKernelGGL(mmpc_tick_kernel, dim3(B), dim3(MMPC_WAVE), 0, st, h->dp, B, d_x, d_tick, d_U_prev, d_glob, nglob, d_obs0, d_vel, d_x_in,
+                       d_traj_ref, d_start, d_obs, d_u_guess, d_x_guess);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipEventRecord(h->ev, st));
+    h->ev_valid = 1; h->last_stream = st;
+    return MMPC_OK;
 }

@@ -16,13 +16,24 @@ Two drivers over the same robots, with bitwise equal per-robot results (tests/te
     stream (mmpc_resume_batch_device) while the others move on, and rejoin two rounds later, one tick behind.  Two handles /
     buffer sets alternate, so that a continuation never shares state with the launch beside it.  Robots do not interact, so
     a robot's sequence of solves - and with it every number it produces - is the same as in lock step.
+
+fused=True (lock step and groups): everything between two solves is one HIP kernel (mmpc_tick_prepare_device, csrc/mmpc_tick.h:
+plant step, clip, nearest plan point, window, obstacle table) instead of the torch expressions of plant() / inputs(); two output
+sets alternate, so the previous optimum is never copied.  warm_start="shifted" (fused only) starts every solve from tick 1 on at
+the previous optimum shifted one stage and its roll-out, which the same kernel writes, with mu_0 = 0.1 (mmpc_set_warm_start):
+the NLP of every tick is unchanged (U_last stays the previous optimum), the iteration counts are less than half.
 """
 import numpy as np
 
 
 class DeviceFleet:
-    def __init__(self, mm, x0, glob, obs0, vel, N=30, device=0, dt=0.1, handles=3):
+    def __init__(self, mm, x0, glob, obs0, vel, N=30, device=0, dt=0.1, handles=3, fused=False, warm_start="reference"):
         import torch
+        if warm_start not in ("reference", "shifted"):
+            raise ValueError("warm_start must be 'reference' or 'shifted', not %r" % (warm_start,))
+        if warm_start == "shifted" and not fused:
+            raise ValueError("warm_start='shifted' needs fused=True: the shifted guess and its roll-out are written by the tick kernel")
+        self.fused, self.warm_start = bool(fused), warm_start
         self.torch = torch
         self.B, self.N, self.M, self.dt = int(x0.shape[0]), int(N), int(obs0.shape[1]), float(dt)
         self.dev = torch.device("cuda", device)
@@ -82,6 +93,11 @@ class DeviceFleet:
         """run_lockstep as a generator: one tick's work is queued on the current stream per next(); the result lands in `res`.
         on_tick(t, u0): called after tick t's solve is queued, on the stream it runs on, with the (B, 5) first inputs - where a
         multi-rank run issues its all-gather of u0 (bench.py --config c5)"""
+        if self.fused:
+            return self._fused_ticks(T, res, on_tick)
+        return self._torch_ticks(T, res, on_tick)
+
+    def _torch_ticks(self, T, res, on_tick=None):
         torch = self.torch
         B, N = self.B, self.N
         eng = self.engs[0]
@@ -105,6 +121,56 @@ class DeviceFleet:
             res.update(u0=hist, x=x, iters=its, all_converged=ok, rounds=T)
             yield t
 
+    def _fused_ticks(self, T, res, on_tick=None):
+        """The same ticks with one mmpc_tick_prepare_device and one solve queued per tick.  x and the tick counters are advanced in
+        place by the kernel of the NEXT tick (after the last one by an advance-only call): res["x"] and res["all_converged"] are those of
+        the whole run and are there once the generator has yielded T - 1."""
+        torch = self.torch
+        B, N, M = self.B, self.N, self.M
+        dev = self.dev
+        eng = self.engs[0]
+        shifted = self.warm_start == "shifted"
+        if not hasattr(self, "_fsets"):
+            mkout = lambda: dict(X=torch.zeros((B, N + 1, 9), **self.f64), U=torch.zeros((B, N, 5), **self.f64), s=torch.zeros((B, N + 1), **self.f64),
+                                 status=torch.zeros(B, dtype=torch.int32, device=dev), iters=torch.zeros(B, dtype=torch.int32, device=dev),
+                                 cost=torch.zeros(B, **self.f64), err=torch.zeros(B, **self.f64))
+            self._fsets = [mkout(), mkout()]
+            self._fin = dict(x_in=torch.zeros((B, 9), **self.f64), loc=torch.zeros((B, N + 1, 9), **self.f64), obs=torch.zeros((B, N + 1, M, 3), **self.f64),
+                             zero=torch.zeros((B, N, 5), **self.f64))
+            if shifted:
+                self._fin.update(ug=torch.zeros((B, N, 5), **self.f64), xg=torch.zeros((B, N + 1, 9), **self.f64))
+        F = self._fin
+        eng.set_iteration_budget(0); eng.reset()
+        x = self.x0.clone()
+        tick = torch.zeros(B, dtype=torch.int64, device=dev)
+        hist = torch.zeros((B, T, 5), **self.f64); its = torch.zeros((B, T), dtype=torch.int32, device=dev)
+        sts = torch.zeros((B, T), dtype=torch.int32, device=dev)
+        ug, xg = (F["ug"], F["xg"]) if shifted else (None, None)
+        prev = None
+        try:
+            for t in range(T):
+                out = self._fsets[t & 1]
+                warm = shifted and prev is not None
+                eng.tick_prepare(x, tick, U_prev=prev, glob=self.glob, obs0=self.obs0, vel=self.vel, x_in=F["x_in"], traj_ref=F["loc"], obs=F["obs"],
+                                 u_guess=ug if warm else None, x_guess=xg if warm else None)
+                if warm and t == 1:
+                    eng.set_warm_start(ug, 0.1)          # (waits for tick 0's solve: the one host synchronisation of a run)
+                eng.solve_batch_device(F["x_in"], F["loc"], self.uref, prev if prev is not None else F["zero"], F["obs"],
+                                       x_guess=xg if warm else None, out=out)
+                prev = out["U"]
+                u0 = prev[:, 0]
+                hist[:, t] = u0; its[:, t] = out["iters"]; sts[:, t] = out["status"]
+                if on_tick is not None:
+                    on_tick(t, u0)
+                if t == T - 1:
+                    eng.tick_prepare(x, tick, U_prev=prev)                             # the plant step after the last tick
+                    res.update(all_converged=(sts == 0).all())
+                res.update(u0=hist, x=x, iters=its, rounds=T)
+                yield t
+        finally:
+            if shifted:
+                eng.set_warm_start(None, 1.0)
+
     # ---- groups in lock step, out of phase
     def run_groups(self, T, groups=2, priority=True, on_tick=None):
         """The fleet as `groups` contiguous groups of robots, each in lock step on its own HIP stream and handle, the streams at
@@ -127,7 +193,7 @@ class DeviceFleet:
             for g in range(G):
                 lo, hi = sharding.shard_bounds(self.B, G, g)
                 sub = DeviceFleet(mm, self.x0[lo:hi], self.glob[lo:hi], self.obs0[lo:hi], self.vel[lo:hi], N=self.N, device=self.dev.index, dt=self.dt,
-                                  handles=1)
+                                  handles=1, fused=self.fused, warm_start=self.warm_start)
                 # (priority: lower number = served first; the last group runs at the default priority)
                 pr = (max(hi_pr, min(lo_pr, 0 - (G - 1 - g))) if hi_pr < 0 else 0) if priority else 0
                 self._groups.append((lo, hi, sub, torch.cuda.Stream(device=self.dev, priority=pr)))
@@ -140,10 +206,14 @@ class DeviceFleet:
             with torch.cuda.stream(st):
                 cb = None if on_tick is None else (lambda t, u0, g=g, lo=lo, hi=hi: on_tick(g, lo, hi, t, u0))
                 gens.append(sub._lockstep_ticks(T, res[g], cb))
-        for t in range(T):
-            for g, (lo, hi, sub, st) in enumerate(self._groups):
-                with torch.cuda.stream(st):
-                    next(gens[g])
+        try:
+            for t in range(T):
+                for g, (lo, hi, sub, st) in enumerate(self._groups):
+                    with torch.cuda.stream(st):
+                        next(gens[g])
+        finally:
+            for gen in gens:             # (a fused sub-fleet puts its handle's warm start back when its generator ends)
+                gen.close()
         for g, (lo, hi, sub, st) in enumerate(self._groups):
             ev = torch.cuda.Event(); ev.record(st); main.wait_event(ev)
             for v in res[g].values():        # (allocated on the group's stream, read on the caller's from here on)
@@ -157,6 +227,9 @@ class DeviceFleet:
 
     # ---- asynchronous
     def run_async(self, T, budget=48, max_rounds=None):
+        if self.fused:
+            raise ValueError("run_async has no fused form: its robots advance under per-robot masks, the tick kernel steps a whole "
+                             "batch (use run_lockstep / run_groups, or fused=False)")
         torch = self.torch
         B, N, M = self.B, self.N, self.M
         dev = self.dev
