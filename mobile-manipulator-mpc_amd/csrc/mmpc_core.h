@@ -274,6 +274,33 @@ struct MmpcIO {
 // uncorrected direction, and for the specialised kernels - which move to a trial point in place - the constraint residuals of the
 // trial point and the running c_soc
 MMPC_HD constexpr int mmpc_soc_doubles(int N, int NX, int NU, int NR) { return (N + 1) * (4 * NX + NU + 1 + 2 * NR) + 8; }
+// Instance b of a batch: the one place where the batch's pointers become an instance's slices (every solve kernel and both
+// runners of the host emulation).  so = doubles of an instance's obstacle table; soc_stride = doubles of its correction scratch.
+// The budget fields are the specialised kernels' own: they set them after the call.  (Filled in place: returned by value the
+// struct travels through a noalias return slot, whose scopes on every access here change the kernels' code.)
+template <int KIND>
+MMPC_DEV void mmpc_instance_io(MmpcIO &io, const MmpcParams &P, int b, int N, size_t so, const double *x_init,
+                               const double *traj_ref, const double *u_ref, const double *u_last, const double *x_guess,
+                               const double *obs, double *X, double *U, double *s, int *status, int *iters, double *cost,
+                               double *err, double *soc, int soc_stride) {
+    typedef MmpcDims<KIND> D;
+    io.x_init = x_init + (size_t)b * D::NX;
+    io.traj_ref = traj_ref + (size_t)b * (N + 1) * D::NREF;
+    io.u_ref = u_ref + (size_t)b * N * D::NU;
+    io.u_last = u_last + (size_t)b * N * D::NU;
+    io.x_guess = x_guess ? x_guess + (size_t)b * (N + 1) * D::NX : nullptr;
+    io.u_guess = P.u_guess ? P.u_guess + (size_t)b * N * D::NU : nullptr;
+    io.obs = obs + (size_t)b * so;
+    io.X = X + (size_t)b * (N + 1) * D::NX;
+    io.U = U + (size_t)b * N * D::NU;
+    io.s = s + (size_t)b * (N + 1);
+    io.status = status + b;
+    io.iters = iters + b;
+    io.cost = cost + b;
+    io.err = err + b;
+    io.state = nullptr; io.budget = 0; io.resume = 0; io.gscr = nullptr;
+    io.soc = soc ? soc + (size_t)b * soc_stride : nullptr;
+}
 
 MMPC_DEV double mmpc_min(double a, double b) { return a < b ? a : b; }
 MMPC_DEV double mmpc_bound_push(double v, double lo, double hi) {

@@ -63,7 +63,7 @@ __device__ unsigned long long mmpc_stamp_acc[16];
 #endif
 #define MMPC_MC_MAX 8    // largest number of circle rows the register-resident path is instantiated for
 
-// (mmpc_sincos: mmpc_core.h)
+// (mmpc_sincos, mmpc_arm_segments: mmpc_core.h)
 // max / min of this path: v_max_f64 / v_min_f64 on the device (the ternary form of mmpc_core.h costs a compare and two selects
 // per use - it hands a NaN in its second argument through; here NaNs are caught by the sums of the evaluation instead, see the
 // status 2 test of the main loop)
@@ -94,19 +94,8 @@ MMPC_DEV double mmpc_log_mant(double m, int *ex) {
     p = fma(p, z, 1.0 / 3.0); p = fma(p, z, 1.0);
     return 2.0 * s * p;
 }
-// planar arm segments (as mmpc_arm_segments in mmpc_core.h) with the light-weight sincos
-MMPC_DEV void mmpc_arm_segments_fast(double q1, double q2, double q3, double dr[3], double dz[3]) {
-    double s1, c1, sA, cA, sB, cB;
-    mmpc_sincos(q1, &s1, &c1);
-    mmpc_sincos(q1 - q2, &sA, &cA);
-    mmpc_sincos(q1 - q2 - q3, &sB, &cB);
-    dr[0] = MMPC_A2 * s1 + MMPC_A3 * c1;
-    dz[0] = MMPC_A2 * c1 - MMPC_A3 * s1;
-    dr[1] = -MMPC_A3 * cA + MMPC_A5 * sA;
-    dz[1] = MMPC_A3 * sA + MMPC_A5 * cA;
-    dr[2] = MMPC_A6 * cB - MMPC_A7 * sB;
-    dz[2] = -MMPC_A6 * sB - MMPC_A7 * cB;
-}
+// (the name under which the primitive tests reach the arm segments of this path, op ARM_FAST of tests/gpu_prim: the one function)
+MMPC_DEV void mmpc_arm_segments_fast(double q1, double q2, double q3, double dr[3], double dz[3]) { mmpc_arm_segments(q1, q2, q3, dr, dz); }
 // state entries the forward kinematics depends on (x, y, psi, q1, q2, q3), as a constant expression
 MMPC_HD constexpr int mmpc_y(int a) { return a < 3 ? a : a + 3; }
 
@@ -676,7 +665,7 @@ MMPC_DEV void mmpc_solve_fast(const MmpcParams &P, const MmpcIO io, double *lds 
         if (NSELF) {
             double dr[3], dz[3], sn, cs;
             mmpc_sincos(xk[2], &sn, &cs);
-            mmpc_arm_segments_fast(xk[NX - 3], xk[NX - 2], xk[NX - 1], dr, dz);
+            mmpc_arm_segments(xk[NX - 3], xk[NX - 2], xk[NX - 1], dr, dz);
 #pragma unroll
             for (int i = 0; i < NSELF; i++) {
                 const double h = mmpc_self_row(i, xk[0], xk[1], cs, sn, dr, dz, nullptr) - S[slack_idx(k)];

@@ -116,7 +116,7 @@
             }
             if (NSELF) {
                 double dr[3], dz[3];
-                mmpc_arm_segments_fast(xk[NX - 3], xk[NX - 2], xk[NX - 1], dr, dz);
+                mmpc_arm_segments(xk[NX - 3], xk[NX - 2], xk[NX - 1], dr, dz);
                 TRG[MMPC_MUL24(k, F::TRGS) + 0] = sn; TRG[MMPC_MUL24(k, F::TRGS) + 1] = cs;
 #pragma unroll
                 for (int a = 0; a < 3; a++) { TRG[MMPC_MUL24(k, F::TRGS) + 2 + a] = dr[a]; TRG[MMPC_MUL24(k, F::TRGS) + 5 + a] = dz[a]; }

@@ -1,6 +1,8 @@
 // mmpc_hip.hip - gfx950 kernels + the C ABI of include/mmpc.h (libmmpc.so).
 // One 64-lane workgroup (= one wavefront) per problem instance; the solver core is
 // mmpc_core.h.  No CPU fallback: every entry point needs a HIP device.
+// From a config to a kernel: mmpc_create resolves the handle's kernels once (resolve_kernels: the generic one, and the specialised
+// pair when MMPC_FAST_LIST has the shape) and keeps them as typed pointers; launch() picks by runs_fast() and launches through them.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdio.h>
@@ -22,7 +24,6 @@ __global__ __launch_bounds__(MMPC_WAVE) void mmpc_solve_kernel(
     int *__restrict__ status, int *__restrict__ iters, double *__restrict__ cost, double *__restrict__ err,
     const int *__restrict__ order, double *__restrict__ soc, int soc_stride) {
     extern __shared__ double lds[];
-    typedef MmpcDims<KIND> D;
     if ((int)blockIdx.x >= B) return;
     // longest-first schedule hint: workgroup i solves instance order[i] (a permutation; results do not depend on it)
     const int b = order ? order[blockIdx.x] : (int)blockIdx.x;
@@ -30,22 +31,8 @@ __global__ __launch_bounds__(MMPC_WAVE) void mmpc_solve_kernel(
     const int N = NC ? NC : P.N, M = MC >= 0 ? MC : P.M;
     const size_t so = (size_t)((OPSC >= 0 ? OPSC : P.obs_per_stage) ? N + 1 : 1) * M * 3;
     MmpcIO io;
-    io.x_init = x_init + (size_t)b * D::NX;
-    io.traj_ref = traj_ref + (size_t)b * (N + 1) * D::NREF;
-    io.u_ref = u_ref + (size_t)b * N * D::NU;
-    io.u_last = u_last + (size_t)b * N * D::NU;
-    io.x_guess = x_guess ? x_guess + (size_t)b * (N + 1) * D::NX : nullptr;
-    io.u_guess = P.u_guess ? P.u_guess + (size_t)b * N * D::NU : nullptr;
-    io.obs = obs + (size_t)b * so;
-    io.X = X + (size_t)b * (N + 1) * D::NX;
-    io.U = U + (size_t)b * N * D::NU;
-    io.s = s + (size_t)b * (N + 1);
-    io.status = status + b;
-    io.iters = iters + b;
-    io.cost = cost + b;
-    io.err = err + b;
-    io.state = nullptr; io.budget = 0; io.resume = 0; io.gscr = nullptr;   // (iteration budgets are a feature of the specialised kernels)
-    io.soc = soc ? soc + (size_t)b * soc_stride : nullptr;
+    mmpc_instance_io<KIND>(io, P, b, N, so, x_init, traj_ref, u_ref, u_last, x_guess, obs, X, U, s, status, iters, cost, err,
+                           soc, soc_stride);
     mmpc_solve_one<KIND, NC, MC, OPSC, LC>(P, io, lds);
 }
 
@@ -59,7 +46,6 @@ __global__ __launch_bounds__(MMPC_WAVE) void mmpc_solve_kernel_static(
     const double *__restrict__ obs, double *__restrict__ X, double *__restrict__ U, double *__restrict__ s,
     int *__restrict__ status, int *__restrict__ iters, double *__restrict__ cost, double *__restrict__ err,
     const int *__restrict__ order, double *__restrict__ soc, int soc_stride) {
-    typedef MmpcDims<KIND> D;
     constexpr int NHS = (KIND == 0 && LC > 0) ? 6 : 0, NQ = (KIND == 0 && AWC && LC >= 2) ? 6 * (LC - 1) : 0;
     __shared__ double lds[mmpc_layout<KIND>(NC, MC, OPSC, NHS, NQ).total];
     if ((int)blockIdx.x >= B) return;
@@ -68,22 +54,8 @@ __global__ __launch_bounds__(MMPC_WAVE) void mmpc_solve_kernel_static(
     constexpr int N = NC, M = MC;
     constexpr size_t so = (size_t)(OPSC ? N + 1 : 1) * M * 3;
     MmpcIO io;
-    io.x_init = x_init + (size_t)b * D::NX;
-    io.traj_ref = traj_ref + (size_t)b * (N + 1) * D::NREF;
-    io.u_ref = u_ref + (size_t)b * N * D::NU;
-    io.u_last = u_last + (size_t)b * N * D::NU;
-    io.x_guess = x_guess ? x_guess + (size_t)b * (N + 1) * D::NX : nullptr;
-    io.u_guess = P.u_guess ? P.u_guess + (size_t)b * N * D::NU : nullptr;
-    io.obs = obs + (size_t)b * so;
-    io.X = X + (size_t)b * (N + 1) * D::NX;
-    io.U = U + (size_t)b * N * D::NU;
-    io.s = s + (size_t)b * (N + 1);
-    io.status = status + b;
-    io.iters = iters + b;
-    io.cost = cost + b;
-    io.err = err + b;
-    io.state = nullptr; io.budget = 0; io.resume = 0; io.gscr = nullptr;
-    io.soc = soc ? soc + (size_t)b * soc_stride : nullptr;
+    mmpc_instance_io<KIND>(io, P, b, N, so, x_init, traj_ref, u_ref, u_last, x_guess, obs, X, U, s, status, iters, cost, err,
+                           soc, soc_stride);
     mmpc_solve_one<KIND, NC, MC, OPSC, LC, AWC>(P, io, lds);
 }
 // (kind, N, M, obs_per_stage, L, as_written): demo_wholebody_qref.py scenario 2 (two planes) as written and with the intended
@@ -106,7 +78,6 @@ __global__ __launch_bounds__(MMPC_WAVE, WPE) void mmpc_fast_kernel(
     const int *__restrict__ order, int budget, double *__restrict__ state, int state_stride, const int *__restrict__ resume_count,
     const int *__restrict__ list_count, double *__restrict__ gscr, double *__restrict__ soc, int soc_stride) {
     __shared__ double lds[mmpc_fast_layout<KIND, N>(MC, OPS).total];
-    typedef MmpcDims<KIND> D;
     // A continuation launch (resume_count != null): `order` is the compacted list of the suspended instances, *resume_count its
     // length, and the grid is SMALL (MMPC_RESUME_GRID workgroups that stride over the list): a handful of instances is left,
     // and a grid of B workgroups that almost all exit at once would still have to be dispatched one by one - in a stream of
@@ -124,25 +95,12 @@ __global__ __launch_bounds__(MMPC_WAVE, WPE) void mmpc_fast_kernel(
         const int M = MC;
         const size_t so = (size_t)(P.obs_per_stage ? N + 1 : 1) * M * 3;
         MmpcIO io;
-        io.x_init = x_init + (size_t)b * D::NX;
-        io.traj_ref = traj_ref + (size_t)b * (N + 1) * D::NX;
-        io.u_ref = u_ref + (size_t)b * N * D::NU;
-        io.u_last = u_last + (size_t)b * N * D::NU;
-        io.x_guess = x_guess ? x_guess + (size_t)b * (N + 1) * D::NX : nullptr;
-        io.u_guess = P.u_guess ? P.u_guess + (size_t)b * N * D::NU : nullptr;
-        io.obs = obs + (size_t)b * so;
-        io.X = X + (size_t)b * (N + 1) * D::NX;
-        io.U = U + (size_t)b * N * D::NU;
-        io.s = s + (size_t)b * (N + 1);
-        io.status = status + b;
-        io.iters = iters + b;
-        io.cost = cost + b;
-        io.err = err + b;
+        mmpc_instance_io<KIND>(io, P, b, N, so, x_init, traj_ref, u_ref, u_last, x_guess, obs, X, U, s, status, iters, cost, err,
+                               soc, soc_stride);
         io.state = state ? state + (size_t)b * state_stride : nullptr;
         io.budget = budget;
         io.resume = resume_count ? 1 : 0;
         io.gscr = MmpcGainBlock<KIND, N>::ON ? gscr + (size_t)b * MmpcGainBlock<KIND, N>::total : nullptr;
-        io.soc = soc ? soc + (size_t)b * soc_stride : nullptr;
         mmpc_solve_fast<KIND, N, MC, CONT, OPS>(P, io, lds);
         if (!CONT || !resume_count) break;      // (one instance per workgroup except in a continuation launch)
         __builtin_amdgcn_s_barrier();           // the next instance reuses the LDS block
@@ -268,14 +226,23 @@ __global__ void mmpc_cold_xguess(int B, int NS, int NX, int clip, const MmpcPara
     }
 }
 
+// the signature of mmpc_solve_kernel<> and mmpc_solve_kernel_static<>, and that of mmpc_fast_kernel<>
+typedef void (*mmpc_gen_fn)(const MmpcParams *, int, const double *, const double *, const double *, const double *, const double *,
+                            const double *, double *, double *, double *, int *, int *, double *, double *, const int *, double *, int);
+typedef void (*mmpc_fast_fn)(const MmpcParams *, int, const double *, const double *, const double *, const double *, const double *,
+                             const double *, double *, double *, double *, int *, int *, double *, double *, const int *, int, double *,
+                             int, const int *, const int *, double *, double *, int);
+
 struct mmpc_handle_s {
     mmpc_config cfg;
     MmpcParams hp;          // host copy
     MmpcParams *dp;         // device copy
     int nx, nu, nref, lds_bytes;
-    int fast;               // 1: specialised kernel exists for (kind, N, M)
+    // the handle's kernels, resolved once by mmpc_create (resolve_kernels)
+    mmpc_gen_fn gen_fn;     // generic: mmpc_solve_kernel<kind>, or the shape's static-LDS instantiation (MMPC_STATIC_LIST)
+    int gen_dyn_lds;        // dynamic LDS of a gen_fn launch: lds_bytes, or 0 for a static-LDS instantiation
+    mmpc_fast_fn fast_fn[2];   // specialised [CONT] for the handle's obs_per_stage; null: (kind, N, M) has none (MMPC_FAST_LIST) or L > 0
     int fast_lds_bytes;
-    int gen_static;    // the shape has a static-LDS instantiation of the generic kernel (MMPC_STATIC_LIST)
     int per_cu, fast_per_cu;   // resident workgroups (= problems) per CU the runtime reports for the two kernels
     int diag;               // weights are diagonal (required by the specialised kernel)
     // one stream at a time: launches of a handle share device state (params, schedule hint, warm start), so work on a
@@ -376,9 +343,43 @@ extern "C" int mmpc_debug_read_gstamps(unsigned long long *out16) {
 extern "C" const char *mmpc_version(void) { return "mmpc 0.1 (gfx950)"; }
 static thread_local char g_err[512] = "";   // errors of the handle-less entry points (mmpc_ik_*)
 extern "C" const char *mmpc_last_error(mmpc_handle h) { return h ? h->err : g_err; }
-static bool runs_fast(mmpc_handle h) { return h->fast && h->diag && !h->hp.terminal_xy_eq && !h->force_generic_env; }
+// this launch uses the specialised kernel (decided per call: weights and the terminal equality change after create)
+static bool runs_fast(mmpc_handle h) { return h->fast_fn[0] && h->diag && !h->hp.terminal_xy_eq && !h->force_generic_env; }
 extern "C" int mmpc_problems_per_cu(mmpc_handle h) { return h ? (runs_fast(h) ? h->fast_per_cu : h->per_cu) : MMPC_E_ARG; }
 extern "C" int mmpc_lds_bytes(mmpc_handle h) { return h ? (runs_fast(h) ? h->fast_lds_bytes : h->lds_bytes) : MMPC_E_ARG; }
+
+// A config becomes its kernels here and nowhere else (cfg, hp and lds_bytes are set): each list is expanded once, the launches
+// go through the pointers.  The static-LDS generic instantiation of a listed shape replaces mmpc_solve_kernel<kind>.
+static void resolve_kernels(mmpc_handle h) {
+    const mmpc_config &c = h->cfg;
+    const MmpcParams &p = h->hp;
+    h->fast_fn[0] = h->fast_fn[1] = nullptr;   // (no list entry for the shape: no specialised kernel, nothing of its sizes)
+    h->fast_lds_bytes = h->state_doubles = h->gscr_doubles = 0;
+    const mmpc_gen_fn by_kind[3] = {mmpc_solve_kernel<0>, mmpc_solve_kernel<1>, mmpc_solve_kernel<2>};
+    h->gen_fn = by_kind[c.kind];
+    h->gen_dyn_lds = h->lds_bytes;
+    if (!getenv("MMPC_NO_STATIC_GENERIC")) {
+#define MMPC_X(K, NN, MM, OO, LL, AA)                                                                                      \
+        if (c.kind == K && c.N == NN && c.M == MM && p.obs_per_stage == OO && c.L == LL && p.as_written == AA) {             \
+            h->gen_fn = mmpc_solve_kernel_static<K, NN, MM, OO, LL, AA>;                                                     \
+            h->gen_dyn_lds = 0;                                                                                              \
+        }
+        MMPC_STATIC_LIST(MMPC_X)
+#undef MMPC_X
+    }
+#define MMPC_X(K, NN, MM, WW)                                                                                              \
+    if (c.kind == K && c.N == NN && c.M == MM && c.L == 0) {                                                                 \
+        const mmpc_fast_fn by_ops[2][2] = {{mmpc_fast_kernel<K, NN, MM, WW, false, 0>, mmpc_fast_kernel<K, NN, MM, WW, true, 0>},  \
+                                           {mmpc_fast_kernel<K, NN, MM, WW, false, 1>, mmpc_fast_kernel<K, NN, MM, WW, true, 1>}}; \
+        h->fast_fn[0] = by_ops[p.obs_per_stage][0];                                                                          \
+        h->fast_fn[1] = by_ops[p.obs_per_stage][1];                                                                          \
+        h->state_doubles = mmpc_fast_state_doubles<K, NN>(MM);                                                               \
+        h->gscr_doubles = MmpcGainBlock<K, NN>::total;                                                                       \
+        h->fast_lds_bytes = mmpc_fast_layout<K, NN>(MM, p.obs_per_stage).total * (int)sizeof(double);                        \
+    }
+    MMPC_FAST_LIST(MMPC_X)
+#undef MMPC_X
+}
 
 extern "C" int mmpc_create(const mmpc_config *cfg, mmpc_handle *out) {
     if (!cfg || !out) return MMPC_E_ARG;
@@ -417,43 +418,11 @@ extern "C" int mmpc_create(const mmpc_config *cfg, mmpc_handle *out) {
                                                         : mmpc_layout<2>(cfg->N, cfg->M, p.obs_per_stage, 0);
     h->lds_bytes = L.total * (int)sizeof(double);
     if (h->lds_bytes > 160 * 1024) return fail(h, MMPC_E_ARG, "problem needs %s bytes of LDS%s", "more than 163840");
-    if (cfg->kind == MMPC_KIND_WHOLEBODY)
-        HIPCHK(h, hipFuncSetAttribute((const void *)mmpc_solve_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, h->lds_bytes));
-    else if (cfg->kind == MMPC_KIND_BASE)
-        HIPCHK(h, hipFuncSetAttribute((const void *)mmpc_solve_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, h->lds_bytes));
-    else
-        HIPCHK(h, hipFuncSetAttribute((const void *)mmpc_solve_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, h->lds_bytes));
-    h->per_cu = 0;
-    if (cfg->kind == MMPC_KIND_WHOLEBODY)
-        HIPCHK(h, hipOccupancyMaxActiveBlocksPerMultiprocessor(&h->per_cu, mmpc_solve_kernel<0>, MMPC_WAVE, h->lds_bytes));
-    else if (cfg->kind == MMPC_KIND_BASE)
-        HIPCHK(h, hipOccupancyMaxActiveBlocksPerMultiprocessor(&h->per_cu, mmpc_solve_kernel<1>, MMPC_WAVE, h->lds_bytes));
-    else
-        HIPCHK(h, hipOccupancyMaxActiveBlocksPerMultiprocessor(&h->per_cu, mmpc_solve_kernel<2>, MMPC_WAVE, h->lds_bytes));
-    h->gen_static = 0;
-    if (!getenv("MMPC_NO_STATIC_GENERIC")) {
-#define MMPC_X(K, NN, MM, OO, LL, AA)                                                                                \
-        if (cfg->kind == K && cfg->N == NN && cfg->M == MM && p.obs_per_stage == OO && cfg->L == LL && p.as_written == AA) {         \
-            h->gen_static = 1;                                                                                         \
-            HIPCHK(h, hipOccupancyMaxActiveBlocksPerMultiprocessor(&h->per_cu, mmpc_solve_kernel_static<K, NN, MM, OO, LL, AA>, MMPC_WAVE, 0)); \
-        }
-        MMPC_STATIC_LIST(MMPC_X)
-#undef MMPC_X
-    }
-    h->fast = 0; h->fast_lds_bytes = 0; h->fast_per_cu = 0;
-    {
-#define MMPC_X(K, NN, MM, WW)                                                                                        \
-        if (cfg->kind == K && cfg->N == NN && cfg->M == MM && cfg->L == 0) {                                                                       \
-            h->fast = 1;                                                                                               \
-            h->state_doubles = mmpc_fast_state_doubles<K, NN>(MM);                                                     \
-            h->gscr_doubles = MmpcGainBlock<K, NN>::total;                                                             \
-            h->fast_lds_bytes = mmpc_fast_layout<K, NN>(MM, p.obs_per_stage).total * (int)sizeof(double);         \
-            if (p.obs_per_stage) HIPCHK(h, hipOccupancyMaxActiveBlocksPerMultiprocessor(&h->fast_per_cu, mmpc_fast_kernel<K, NN, MM, WW, false, 1>, MMPC_WAVE, 0)); \
-            else HIPCHK(h, hipOccupancyMaxActiveBlocksPerMultiprocessor(&h->fast_per_cu, mmpc_fast_kernel<K, NN, MM, WW, false, 0>, MMPC_WAVE, 0)); \
-        }
-        MMPC_FAST_LIST(MMPC_X)
-#undef MMPC_X
-    }
+    resolve_kernels(h);
+    h->per_cu = h->fast_per_cu = 0;
+    if (h->gen_dyn_lds) HIPCHK(h, hipFuncSetAttribute((const void *)h->gen_fn, hipFuncAttributeMaxDynamicSharedMemorySize, h->gen_dyn_lds));
+    HIPCHK(h, hipOccupancyMaxActiveBlocksPerMultiprocessor(&h->per_cu, h->gen_fn, MMPC_WAVE, h->gen_dyn_lds));
+    if (h->fast_fn[0]) HIPCHK(h, hipOccupancyMaxActiveBlocksPerMultiprocessor(&h->fast_per_cu, h->fast_fn[0], MMPC_WAVE, 0));
     const size_t B = (size_t)cfg->max_batch, N = (size_t)cfg->N, nx = (size_t)h->nx, nu = (size_t)h->nu;
     const size_t nobs = (size_t)(p.obs_per_stage ? N + 1 : 1) * (size_t)cfg->M * 3;
     HIPCHK(h, hipMalloc(&h->dp, sizeof(MmpcParams)));
@@ -474,7 +443,7 @@ extern "C" int mmpc_create(const mmpc_config *cfg, mmpc_handle *out) {
     HIPCHK(h, hipMalloc(&h->d_order, B * 4));
     HIPCHK(h, hipMalloc(&h->d_warm, B * 4));
     HIPCHK(h, hipMalloc(&h->d_key, B * 4));
-    if (h->fast && h->gscr_doubles) HIPCHK(h, hipMalloc(&h->d_gscr, B * (size_t)h->gscr_doubles * 8));
+    if (h->fast_fn[0] && h->gscr_doubles) HIPCHK(h, hipMalloc(&h->d_gscr, B * (size_t)h->gscr_doubles * 8));
     h->soc_doubles = mmpc_soc_doubles(cfg->N, h->nx, h->nu, L.NR);
     HIPCHK(h, hipMalloc(&h->d_soc, B * (size_t)h->soc_doubles * 8));
     h->order_B = 0;
@@ -541,14 +510,30 @@ extern "C" int mmpc_reset(mmpc_handle h) {
     return MMPC_OK;
 }
 
-static int launch(mmpc_handle h, int B, const double *x_init, const double *traj, const double *uref, const double *ulast,
-                  const double *xguess, const double *obs, double *X, double *U, double *s, int *status, int *iters,
-                  double *cost, double *err, hipStream_t st, bool resume = false, const int *ulist = nullptr, const int *ucount = nullptr,
-                  int ucap = 0) {
+// the device pointers of a batch, as the *_device entry points take them
+struct MmpcBatch {
+    const double *x_init, *traj, *uref, *ulast, *xguess, *obs;
+    double *X, *U, *s;
+    int *status, *iters;
+    double *cost, *err;
+};
+// what a launch covers: the whole batch, the instances the budgeted launch before it left suspended (a continuation), or the
+// rows of a caller's device list (list launches only: `count` on the device, the grid is `capacity`)
+enum MmpcCover { MMPC_WHOLE_BATCH, MMPC_CONTINUATION, MMPC_LIST };
+struct MmpcMode {
+    MmpcCover cover;
+    const int *list, *count;
+    int capacity;
+};
+static const MmpcMode whole_batch = {MMPC_WHOLE_BATCH, nullptr, nullptr, 0}, continuation = {MMPC_CONTINUATION, nullptr, nullptr, 0};
+
+static int launch(mmpc_handle h, int B, const MmpcBatch &a, hipStream_t st, const MmpcMode &mode) {
+    const bool resume = mode.cover == MMPC_CONTINUATION;
+    const int *ulist = mode.cover == MMPC_LIST ? mode.list : nullptr, *ucount = ulist ? mode.count : nullptr;
     // (the X guess is a launch argument: null = tile(x_init); nothing in the device parameter block changes per launch)
     // a launch on another stream than the previous one waits for it: both touch the handle's schedule hint
     if (h->ev_valid && st != h->last_stream) HIPCHK(h, hipStreamWaitEvent(st, h->ev, 0));
-    const bool use_fast = h->fast && h->diag && !h->hp.terminal_xy_eq && !h->force_generic_env;
+    const bool use_fast = runs_fast(h);
     // a continuation belongs to the budgeted launch right before it (same B, same buffers): anything in between - another
     // launch, a reset, a change of the budget, a first continuation - leaves the save areas and the list stale
     if (resume && !(use_fast && h->d_state && h->resume_B == B))
@@ -562,55 +547,32 @@ static int launch(mmpc_handle h, int B, const double *x_init, const double *traj
     const int key_planes = (h->cfg.kind == MMPC_KIND_WHOLEBODY && h->hp.L > 0) ? h->hp.L : 0;
     if (lpt && !history && (h->cfg.M > 0 || key_planes)) {
         hipLaunchKernelGGL(mmpc_difficulty_key, dim3((B + 63) / 64), dim3(64), 0, st, B, h->cfg.N, h->cfg.M, h->nref,
-                           h->hp.obs_per_stage, traj, obs, h->d_key, h->dp, x_init, key_planes);
+                           h->hp.obs_per_stage, a.traj, a.obs, h->d_key, h->dp, a.x_init, key_planes);
         hipLaunchKernelGGL(mmpc_lpt_order, dim3(1), dim3(MMPC_LPT_THREADS), 0, st, B, h->d_key, h->d_order);
     }
     const int *order = ulist ? ulist : ((history || (lpt && (h->cfg.M > 0 || key_planes))) ? h->d_order : nullptr);
-    const int grid = ulist ? ucap : B;
+    const int grid = ulist ? mode.capacity : B;
     if (use_fast) {
-#define MMPC_LAUNCH_FAST(K, NN, MM, WW, OPS)                                                                              \
-            if (resume || h->budget > 0)                                                                                               \
-                hipLaunchKernelGGL((mmpc_fast_kernel<K, NN, MM, WW, true, OPS>), dim3(resume ? (B < MMPC_RESUME_GRID ? B : MMPC_RESUME_GRID) : grid), dim3(MMPC_WAVE), 0, st, h->dp, B, \
-                                   x_init, traj, uref, ulast, xguess, obs, X, U, s, status, iters, cost, err, resume ? h->d_list : order, \
-                                   resume ? 0 : h->budget, h->d_state, h->state_doubles, resume ? h->d_count : (const int *)nullptr,      \
-                                   resume ? (const int *)nullptr : ucount, h->d_gscr, h->d_soc, h->soc_doubles);                                                    \
-            else                                                                                                                       \
-                hipLaunchKernelGGL((mmpc_fast_kernel<K, NN, MM, WW, false, OPS>), dim3(grid), dim3(MMPC_WAVE), 0, st, h->dp, B,           \
-                                   x_init, traj, uref, ulast, xguess, obs, X, U, s, status, iters, cost, err, order, 0,                  \
-                                   (double *)nullptr, 0, (const int *)nullptr, ucount, h->d_gscr, h->d_soc, h->soc_doubles);
-#define MMPC_X(K, NN, MM, WW)                                                                                          \
-        if (h->cfg.kind == K && h->cfg.N == NN && h->cfg.M == MM) {                                                   \
-            if (h->cfg.obs_per_stage) { MMPC_LAUNCH_FAST(K, NN, MM, WW, 1) } else { MMPC_LAUNCH_FAST(K, NN, MM, WW, 0) }   \
-        }
-        MMPC_FAST_LIST(MMPC_X)
-#undef MMPC_X
-#undef MMPC_LAUNCH_FAST
-    } else if (h->gen_static) {
-#define MMPC_X(K, NN, MM, OO, LL, AA)                                                                                \
-        if (h->cfg.kind == K && h->cfg.N == NN && h->cfg.M == MM && h->hp.obs_per_stage == OO && h->cfg.L == LL && h->hp.as_written == AA) \
-            hipLaunchKernelGGL((mmpc_solve_kernel_static<K, NN, MM, OO, LL, AA>), dim3(B), dim3(MMPC_WAVE), 0, st, h->dp, B, x_init, traj, \
-                               uref, ulast, xguess, obs, X, U, s, status, iters, cost, err, order, h->d_soc, h->soc_doubles);
-        MMPC_STATIC_LIST(MMPC_X)
-#undef MMPC_X
-    } else if (h->cfg.kind == MMPC_KIND_WHOLEBODY)
-        hipLaunchKernelGGL(mmpc_solve_kernel<0>, dim3(B), dim3(MMPC_WAVE), h->lds_bytes, st, h->dp, B, x_init, traj, uref,
-                           ulast, xguess, obs, X, U, s, status, iters, cost, err, order, h->d_soc, h->soc_doubles);
-    else if (h->cfg.kind == MMPC_KIND_BASE)
-        hipLaunchKernelGGL(mmpc_solve_kernel<1>, dim3(B), dim3(MMPC_WAVE), h->lds_bytes, st, h->dp, B, x_init, traj, uref,
-                           ulast, xguess, obs, X, U, s, status, iters, cost, err, order, h->d_soc, h->soc_doubles);
-    else
-        hipLaunchKernelGGL(mmpc_solve_kernel<2>, dim3(B), dim3(MMPC_WAVE), h->lds_bytes, st, h->dp, B, x_init, traj, uref,
-                           ulast, xguess, obs, X, U, s, status, iters, cost, err, order, h->d_soc, h->soc_doubles);
+        // CONT instantiation: the launch may suspend (a budget is set) or continues suspended instances; only it gets the save areas
+        const bool cont = resume || h->budget > 0;
+        hipLaunchKernelGGL(h->fast_fn[cont], dim3(resume ? (B < MMPC_RESUME_GRID ? B : MMPC_RESUME_GRID) : grid), dim3(MMPC_WAVE), 0, st,
+                           h->dp, B, a.x_init, a.traj, a.uref, a.ulast, a.xguess, a.obs, a.X, a.U, a.s, a.status, a.iters, a.cost, a.err,
+                           resume ? h->d_list : order, resume ? 0 : h->budget, cont ? h->d_state : (double *)nullptr,
+                           cont ? h->state_doubles : 0, resume ? h->d_count : (const int *)nullptr,
+                           resume ? (const int *)nullptr : ucount, h->d_gscr, h->d_soc, h->soc_doubles);
+    } else
+        hipLaunchKernelGGL(h->gen_fn, dim3(B), dim3(MMPC_WAVE), h->gen_dyn_lds, st, h->dp, B, a.x_init, a.traj, a.uref, a.ulast,
+                           a.xguess, a.obs, a.X, a.U, a.s, a.status, a.iters, a.cost, a.err, order, h->d_soc, h->soc_doubles);
     HIPCHK(h, hipGetLastError());
     if (use_fast && h->budget > 0 && !resume) {
         // who is suspended: compacted list for mmpc_resume_batch_device
         HIPCHK(h, hipMemsetAsync(h->d_count, 0, 4, st));
-        if (ulist) hipLaunchKernelGGL(mmpc_collect_suspended_list, dim3((ucap + 255) / 256), dim3(256), 0, st, B, ulist, ucount, status, h->d_list, h->d_count);
-        else hipLaunchKernelGGL(mmpc_collect_suspended, dim3((B + 255) / 256), dim3(256), 0, st, B, status, h->d_list, h->d_count);
+        if (ulist) hipLaunchKernelGGL(mmpc_collect_suspended_list, dim3((mode.capacity + 255) / 256), dim3(256), 0, st, B, ulist, ucount, a.status, h->d_list, h->d_count);
+        else hipLaunchKernelGGL(mmpc_collect_suspended, dim3((B + 255) / 256), dim3(256), 0, st, B, a.status, h->d_list, h->d_count);
         h->resume_B = B;
     }
     if (lpt && h->hint_on == 1) {
-        hipLaunchKernelGGL(mmpc_lpt_order, dim3(1), dim3(MMPC_LPT_THREADS), 0, st, B, iters, h->d_order);
+        hipLaunchKernelGGL(mmpc_lpt_order, dim3(1), dim3(MMPC_LPT_THREADS), 0, st, B, a.iters, h->d_order);
         h->order_B = B;
     }
     HIPCHK(h, hipEventRecord(h->ev, st));
@@ -618,9 +580,21 @@ static int launch(mmpc_handle h, int B, const double *x_init, const double *traj
     return MMPC_OK;
 }
 
+// the argument check the three *_device entry points share (the obstacle table may be null when there are no obstacles)
+static bool bad_batch(mmpc_handle h, int B, const MmpcBatch &a) {
+    return !h || B < 1 || B > h->cfg.max_batch || !a.x_init || !a.traj || !a.uref || !a.ulast || !a.X || !a.U || !a.s || !a.status ||
+           !a.iters || !a.cost || !a.err || (h->cfg.M > 0 && !a.obs);
+}
+// ... and their launch: on the handle's device, with the handle's (unread) table in place of a null one
+static int launch_device(mmpc_handle h, int B, MmpcBatch a, void *stream, const MmpcMode &mode) {
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    if (!a.obs) a.obs = h->d_obs;
+    return launch(h, B, a, (hipStream_t)stream, mode);
+}
+
 extern "C" int mmpc_set_iteration_budget(mmpc_handle h, int budget) {
     if (!h || budget < 0) return fail(h, MMPC_E_ARG, "mmpc_set_iteration_budget: %s%s", "budget must be >= 0");
-    if (budget > 0 && !h->fast) return fail(h, MMPC_E_UNSUPPORTED, "mmpc_set_iteration_budget: %s%s", "this (kind, N, M) runs the generic kernel, which has no continuation");
+    if (budget > 0 && !h->fast_fn[0]) return fail(h, MMPC_E_UNSUPPORTED, "mmpc_set_iteration_budget: %s%s", "this (kind, N, M) runs the generic kernel, which has no continuation");
     HIPCHK(h, hipSetDevice(h->cfg.device));
     if (budget > 0 && !h->d_state) {
         const size_t B = (size_t)h->cfg.max_batch;
@@ -641,12 +615,9 @@ extern "C" int mmpc_resume_batch_device(mmpc_handle h, int B, const double *d_x_
                                         const double *d_obs, double *d_X, double *d_U, double *d_s, int *d_status,
                                         int *d_iters, double *d_cost, double *d_err, void *stream) {
     if (h && B == 0) return MMPC_OK;   // an empty batch (e.g. the shard of a rank beyond the batch) is a no-op
-    if (!h || B < 1 || B > h->cfg.max_batch || !d_x_init || !d_traj_ref || !d_u_ref || !d_u_last || !d_X || !d_U || !d_s ||
-        !d_status || !d_iters || !d_cost || !d_err || (h->cfg.M > 0 && !d_obs))
-        return fail(h, MMPC_E_ARG, "mmpc_resume_batch_device: %s%s", "bad argument");
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    return launch(h, B, d_x_init, d_traj_ref, d_u_ref, d_u_last, d_x_guess, d_obs ? d_obs : h->d_obs, d_X, d_U, d_s,
-                  d_status, d_iters, d_cost, d_err, (hipStream_t)stream, true);
+    const MmpcBatch a = {d_x_init, d_traj_ref, d_u_ref, d_u_last, d_x_guess, d_obs, d_X, d_U, d_s, d_status, d_iters, d_cost, d_err};
+    if (bad_batch(h, B, a)) return fail(h, MMPC_E_ARG, "mmpc_resume_batch_device: %s%s", "bad argument");
+    return launch_device(h, B, a, stream, continuation);
 }
 
 extern "C" int mmpc_suspended_count(mmpc_handle h, int *count) {
@@ -682,24 +653,19 @@ extern "C" int mmpc_solve_batch_device(mmpc_handle h, int B, const double *d_x_i
     if (h && B == 0) return MMPC_OK;   // an empty batch (e.g. the shard of a rank beyond the batch) is a no-op
     // B > max_batch: the handle's per-instance buffers (launch order, difficulty keys, save areas of suspended solves, list of
     // the suspended, the opt-in U guess) are sized for max_batch instances
-    if (!h || B < 1 || B > h->cfg.max_batch || !d_x_init || !d_traj_ref || !d_u_ref || !d_u_last || !d_X || !d_U || !d_s || !d_status ||
-        !d_iters || !d_cost || !d_err || (h->cfg.M > 0 && !d_obs))
-        return fail(h, MMPC_E_ARG, "mmpc_solve_batch_device: %s%s", "bad argument (B must be in 1..max_batch)");
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    return launch(h, B, d_x_init, d_traj_ref, d_u_ref, d_u_last, d_x_guess, d_obs ? d_obs : h->d_obs, d_X, d_U, d_s,
-                  d_status, d_iters, d_cost, d_err, (hipStream_t)stream);
+    const MmpcBatch a = {d_x_init, d_traj_ref, d_u_ref, d_u_last, d_x_guess, d_obs, d_X, d_U, d_s, d_status, d_iters, d_cost, d_err};
+    if (bad_batch(h, B, a)) return fail(h, MMPC_E_ARG, "mmpc_solve_batch_device: %s%s", "bad argument (B must be in 1..max_batch)");
+    return launch_device(h, B, a, stream, whole_batch);
 }
 
 extern "C" int mmpc_solve_list_device(mmpc_handle h, int B, const int *d_list, const int *d_count, int capacity, const double *d_x_init,
                                       const double *d_traj_ref, const double *d_u_ref, const double *d_u_last, const double *d_x_guess,
                                       const double *d_obs, double *d_X, double *d_U, double *d_s, int *d_status, int *d_iters,
                                       double *d_cost, double *d_err, void *stream) {
-    if (!h || B < 1 || B > h->cfg.max_batch || !d_list || !d_count || capacity < 1 || capacity > B || !d_x_init || !d_traj_ref || !d_u_ref ||
-        !d_u_last || !d_X || !d_U || !d_s || !d_status || !d_iters || !d_cost || !d_err || (h->cfg.M > 0 && !d_obs))
+    const MmpcBatch a = {d_x_init, d_traj_ref, d_u_ref, d_u_last, d_x_guess, d_obs, d_X, d_U, d_s, d_status, d_iters, d_cost, d_err};
+    if (bad_batch(h, B, a) || !d_list || !d_count || capacity < 1 || capacity > B)
         return fail(h, MMPC_E_ARG, "mmpc_solve_list_device: %s%s", "bad argument (B in 1..max_batch, 1 <= capacity <= B)");
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    return launch(h, B, d_x_init, d_traj_ref, d_u_ref, d_u_last, d_x_guess, d_obs ? d_obs : h->d_obs, d_X, d_U, d_s,
-                  d_status, d_iters, d_cost, d_err, (hipStream_t)stream, false, d_list, d_count, capacity);
+    return launch_device(h, B, a, stream, MmpcMode{MMPC_LIST, d_list, d_count, capacity});
 }
 
 extern "C" int mmpc_solve_batch(mmpc_handle h, int B, const double *x_init, const double *traj_ref, const double *u_ref,
@@ -725,12 +691,12 @@ extern "C" int mmpc_solve_batch(mmpc_handle h, int B, const double *x_init, cons
                            h->dp, h->d_warm, h->d_x_init, h->d_xguess);
         xg = h->d_xguess;
     }
-    int rc = launch(h, B, h->d_x_init, h->d_traj, h->d_uref, h->d_ulatest, xg, h->d_obs, h->d_X, h->d_U, h->d_s,
-                    h->d_status, h->d_iters, h->d_cost, h->d_err, st);
+    const MmpcBatch a = {h->d_x_init, h->d_traj, h->d_uref, h->d_ulatest, xg, h->d_obs, h->d_X, h->d_U, h->d_s,
+                         h->d_status, h->d_iters, h->d_cost, h->d_err};
+    int rc = launch(h, B, a, st, whole_batch);
     if (rc) return rc;
-    if (h->budget > 0 && h->fast && h->d_state) {   // the host-pointer call returns finished solves: continue the suspended ones at once
-        rc = launch(h, B, h->d_x_init, h->d_traj, h->d_uref, h->d_ulatest, xg, h->d_obs, h->d_X, h->d_U, h->d_s,
-                    h->d_status, h->d_iters, h->d_cost, h->d_err, st, true);
+    if (h->budget > 0 && h->fast_fn[0] && h->d_state) {   // the host-pointer call returns finished solves: continue the suspended ones at once
+        rc = launch(h, B, a, st, continuation);
         if (rc && rc != MMPC_E_UNSUPPORTED) return rc;
     }
     // u_latest <- U*, x_guess <- X*  (:329-330), for the instances that converged

@@ -23,24 +23,14 @@ static void run(const MmpcParams *P, int B, const double *x_init, const double *
         // exact-size heap slab so that ASAN sees any out-of-slab access
         double *lds = (double *)malloc(sizeof(double) * L.total);
         for (int i = 0; i < L.total; i++) lds[i] = NAN;
-        MmpcIO io;
-        io.x_init = x_init + (size_t)b * D::NX;
-        io.traj_ref = traj_ref + (size_t)b * (N + 1) * D::NREF;
-        io.u_ref = u_ref + (size_t)b * N * D::NU;
-        io.u_last = u_last + (size_t)b * N * D::NU;
-        io.x_guess = x_guess ? x_guess + (size_t)b * (N + 1) * D::NX : nullptr;
-        io.u_guess = P->u_guess ? P->u_guess + (size_t)b * N * D::NU : nullptr;
-        io.obs = obs + (size_t)b * so;
-        io.X = X + (size_t)b * (N + 1) * D::NX;
-        io.U = U + (size_t)b * N * D::NU;
-        io.s = s + (size_t)b * (N + 1);
-        io.status = status + b; io.iters = iters + b; io.cost = cost + b; io.err = err + b;
-        io.state = nullptr; io.budget = 0; io.resume = 0; io.gscr = nullptr;
         // scratch of the second-order correction (global memory on the device), exact size as the slab
         const int sdn = mmpc_soc_doubles(N, D::NX, D::NU, L.NR);
         double *soc = (double *)malloc(sizeof(double) * sdn);
         for (int i = 0; i < sdn; i++) soc[i] = NAN;
-        io.soc = soc;
+        // (the scratch is this instance's own: stride 0)
+        MmpcIO io;
+        mmpc_instance_io<KIND>(io, *P, b, N, so, x_init, traj_ref, u_ref, u_last, x_guess, obs, X, U, s, status, iters, cost, err,
+                               soc, 0);
         MmpcEmu emu = reverse ? MmpcEmu{63, -1, -1} : MmpcEmu{0, 64, 1};
         mmpc_solve_one<KIND>(*P, io, lds, emu);
         free(soc);
@@ -60,31 +50,20 @@ static void run_fast(const MmpcParams *P, int B, const double *x_init, const dou
     for (int b = 0; b < B; b++) {
         double *lds = (double *)malloc(sizeof(double) * L.total);
         for (int i = 0; i < L.total; i++) lds[i] = NAN;
-        MmpcIO io;
-        io.x_init = x_init + (size_t)b * D::NX;
-        io.traj_ref = traj_ref + (size_t)b * (N + 1) * D::NX;
-        io.u_ref = u_ref + (size_t)b * N * D::NU;
-        io.u_last = u_last + (size_t)b * N * D::NU;
-        io.x_guess = x_guess ? x_guess + (size_t)b * (N + 1) * D::NX : nullptr;
-        io.u_guess = P->u_guess ? P->u_guess + (size_t)b * N * D::NU : nullptr;
-        io.obs = obs + (size_t)b * so;
-        io.X = X + (size_t)b * (N + 1) * D::NX;
-        io.U = U + (size_t)b * N * D::NU;
-        io.s = s + (size_t)b * (N + 1);
-        io.status = status + b; io.iters = iters + b; io.cost = cost + b; io.err = err + b;
         const int sd = mmpc_fast_state_doubles<KIND, N>(MC);
-        io.state = state ? state + (size_t)b * sd : nullptr; io.budget = budget; io.resume = resume;
         if (resume && status[b] != 3) { free(lds); continue; }   // a continuation launch only runs the suspended instances
         MmpcEmu emu = reverse ? MmpcEmu{63, -1, -1} : MmpcEmu{0, 64, 1};
         // gain block of the long horizons (global memory on the device)
         const int gd = MmpcGainBlock<KIND, N>::total;
         double *gscr = gd ? (double *)malloc(sizeof(double) * gd) : nullptr;
         for (int i = 0; i < gd; i++) gscr[i] = NAN;
-        io.gscr = gscr;
         const int sdn = mmpc_soc_doubles(N, D::NX, D::NU, MC + D::NSELF);
         double *soc = (double *)malloc(sizeof(double) * sdn);
         for (int i = 0; i < sdn; i++) soc[i] = NAN;
-        io.soc = soc;
+        MmpcIO io;
+        mmpc_instance_io<KIND>(io, *P, b, N, so, x_init, traj_ref, u_ref, u_last, x_guess, obs, X, U, s, status, iters, cost, err,
+                               soc, 0);
+        io.state = state ? state + (size_t)b * sd : nullptr; io.budget = budget; io.resume = resume; io.gscr = gscr;   // (as mmpc_fast_kernel)
         if (budget > 0 || resume) mmpc_solve_fast<KIND, N, MC, true>(*P, io, lds, emu); else mmpc_solve_fast<KIND, N, MC, false>(*P, io, lds, emu);
         free(gscr); free(soc);
         free(lds);
