@@ -11,7 +11,8 @@
  *
  * Array conventions are the reference's: float64, C order, one record per problem instance:
  *   x_init[B][nx]  traj_ref[B][N+1][nx]  u_ref[B][N][nu]  obs[B][M][3] = (x, y, radius)
- *   (or obs[B][N+1][M][3] when cfg.obs_per_stage: per-stage centres for moving obstacles)
+ *   (or obs[B][N+1][M][3] when cfg.obs_per_stage = 1: per-stage centres for moving obstacles;
+ *    or obs[B][M][5] = (x, y, radius, v_x, v_y) when cfg.obs_per_stage = 2: linear motion, see mmpc_set_obstacle_clock)
  *   X[B][N+1][nx]  U[B][N][nu]  s[B][N+1]
  * whole-body kind: nx=9 [x,y,psi,dx,dy,dpsi,q1,q2,q3], nu=5 [dV,dw,dq1,dq2,dq3]
  * (robot_models/mobile_manipulator.py:22,62-65); base kind: nx=6, nu=2 (robot_models/base.py:26).
@@ -53,12 +54,19 @@ typedef struct mmpc_config {
                           Envelope: mmpc_create accepts a config when, besides these ranges, the generic kernel's LDS slab for it
                           (mmpc_lds_bytes of a handle that runs the generic kernel) is at most 160 KiB; otherwise it returns
                           MMPC_E_ARG with an error that names LDS.  Largest N at M = 0 / 5 / 8 / 16:
-                            whole-body         49 / 44 / 41 / 35    (obs_per_stage: 49 / 42 / 39 / 32)
-                            base               63 / 63 / 63 / 59    (obs_per_stage: 63 / 63 / 63 / 51; N = 63 up to M = 13, 10)
-                            pose-reference     55 / 49 / 45 / 38    (obs_per_stage: 55 / 47 / 43 / 35)
+                            whole-body         49 / 44 / 41 / 35    (obs_per_stage = 1: 49 / 42 / 39 / 32)
+                            base               63 / 63 / 63 / 59    (obs_per_stage = 1: 63 / 63 / 63 / 51; N = 63 up to M = 13, 10)
+                            pose-reference     55 / 49 / 45 / 38    (obs_per_stage = 1: 55 / 47 / 43 / 35)
+                          obs_per_stage = 2 (the motion record: 2 M + 1 doubles more than the static one) has the rows of
+                          obs_per_stage = 0:  49 / 44 / 41 / 35,  63 / 63 / 63 / 59 (N = 63 up to M = 13),  55 / 49 / 45 / 38.
                           Half-space planes at N = 20: intended rows fit for L <= 8 at any M; as written, L = 5 fits up to
                           M = 10, L = 6 up to M = 3, L = 7 and 8 never; at N = 30, as-written L = 2 fits with M = 0 only. */
-    int obs_per_stage; /* 0: obs[B][M][3]; 1: obs[B][N+1][M][3] */
+    int obs_per_stage; /* 0: obs[B][M][3]; 1: obs[B][N+1][M][3]; 2: the motion record obs[B][M][5] = (c_x, c_y, r, v_x, v_y) - the
+                          kernels form the centre of obstacle m at stage k where they read it, (c_x + v_x t_k, c_y + v_y t_k) with
+                          t_k = (double)(tick_b + k) dt, every operation rounded on its own (no fused multiply-add): the very
+                          centres of step 5 of mmpc_tick_prepare_device, so a solve equals the solve of that table bit for bit.
+                          tick_b comes from mmpc_set_obstacle_clock (default 0: the record is "position now").  Every solve
+                          entry point takes the record where it takes the table.  Any other value is MMPC_E_ARG */
     int max_batch;     /* capacity of the device-side buffers: warm start, outputs of the host-pointer call, launch order and - for
                           horizons N >= 21 on a specialised kernel - one 8 (N nu (nx + 1) + N nu (nu - 1) / 2 + 64) byte block of
                           feedback gains per instance (14.9 KB at N = 30: 122 MB for 8192 instances) */
@@ -161,6 +169,15 @@ int mmpc_ik_batch_device(int device, int B, const double *d_q0, const double *d_
  * in fewer than half the iterations.  mmpc_set_warm_start(h, NULL, 1.0) restores the default. */
 int mmpc_set_warm_start(mmpc_handle h, const double *d_u_guess, double mu_init);
 
+/* The clock of the motion record (handles created with obs_per_stage = 2; MMPC_E_UNSUPPORTED on any other).  d_tick [max_batch]
+ * (device memory, int64, one tick count per instance ROW - list launches and continuations index it like every other
+ * per-instance array) stays registered until it is replaced; the kernels read it at launch time, so a caller that keeps the
+ * counts current on the device registers it once: it is the very array mmpc_tick_prepare_device advances.  NULL (the default)
+ * means tick 0 for every instance.  Range: 0 <= tick < 2^52 (a kernel may form (double)(tick + k) as (double)tick + (double)k,
+ * which is exact there).  The call waits for the handle's launches in flight.  A caller with tracker output ("where the
+ * obstacle is now and how fast it moves") fills the record per solve and leaves the clock at NULL. */
+int mmpc_set_obstacle_clock(mmpc_handle h, const long long *d_tick);
+
 /* Launch order of the workgroups (= instances) of a batch.  A batch takes as long as its last wave, so the instances
  * that need the most interior-point iterations should start first.  mode 1 (default): longest-first by the iteration counts
  * of the handle's previous launch of the same B when there is one (a receding-horizon loop solves the same robots every
@@ -190,7 +207,7 @@ int mmpc_suspended_count(mmpc_handle h, int *count);
 
 /* The glue of one receding-horizon tick for B robots that stay in device memory between ticks (no reference counterpart as
  * a batch; per robot it is the reference's closed loop without the simulator, interface_wholebody_qref.py:100-143).  Whole-body
- * handles created with obs_per_stage = 1 only (MMPC_E_UNSUPPORTED otherwise); N, M, dt and xlim come from the handle.  One
+ * handles created with obs_per_stage = 1 or 2 only (MMPC_E_UNSUPPORTED otherwise); N, M, dt and xlim come from the handle.  One
  * launch, one 64-lane workgroup per robot b:
  *   1. advance - skipped when d_U_prev is NULL (before the first tick): x_b <- f(clip(x_b, xlim), U_prev[b][0]) with the plant
  *      step of robot_models/mobile_manipulator.py (every operation rounded on its own, no fused multiply-add), tick_b <- tick_b + 1;
@@ -200,7 +217,8 @@ int mmpc_suspended_count(mmpc_handle h, int *count);
  *      j = 0 and its NaN reaches the solve, which reports MMPC_STATUS_NUMERIC for it alone;
  *   4. d_traj_ref[b][k] = glob[b][min(j + k, nglob - 1)], k = 0..N; d_start[b] = j (int32);
  *   5. d_obs[b][k][m] = (c_x + v_x t_k, c_y + v_y t_k, r), t_k = (double)(tick_b + k) dt, from d_obs0[B][M][3] = (c_x, c_y, r) and
- *      d_vel[B][M][2];
+ *      d_vel[B][M][2] - on a handle with obs_per_stage = 2 there is no table: d_obs must be NULL (MMPC_E_ARG otherwise) and
+ *      the solve forms the same centres from its record and d_tick, registered once with mmpc_set_obstacle_clock;
  *   6. shifted warm start - only when d_U_prev, d_u_guess and d_x_guess are all given: u_guess[k] = U_prev[k + 1] for k < N - 1,
  *      u_guess[N - 1] = U_prev[N - 1]; x_guess[0] = x_in, x_guess[k + 1] = f(x_guess[k], u_guess[k]): the initial point that
  *      mmpc_set_warm_start describes (register d_u_guess there, pass d_x_guess to the solve).  d_u_guess must not be d_U_prev.
@@ -219,7 +237,7 @@ int mmpc_tick_prepare_device(mmpc_handle h, int B, double *d_x, long long *d_tic
  * warm start).  Calls on one handle must come from one host thread at a time.  Launches may use different streams:
  * a launch on another stream than the handle's previous one is ordered after it (event wait), and the entry points
  * that change the parameter block or the warm start (mmpc_set_weights, mmpc_set_terminal_xy_equality,
- * mmpc_set_warm_start, mmpc_reset, mmpc_get/set_u_latest) wait for the handle's launches in flight first. */
+ * mmpc_set_warm_start, mmpc_set_obstacle_clock, mmpc_reset, mmpc_get/set_u_latest) wait for the handle's launches in flight first. */
 
 /* bytes of LDS one problem instance occupies (one 64-lane workgroup) */
 int mmpc_lds_bytes(mmpc_handle h);

@@ -24,7 +24,7 @@ class MmpcConfig(C.Structure):
 EXPORTS = ["mmpc_create", "mmpc_destroy", "mmpc_set_weights", "mmpc_set_terminal_xy_equality", "mmpc_reset",
            "mmpc_solve_batch", "mmpc_solve_batch_device", "mmpc_get_u_latest", "mmpc_set_u_latest",
            "mmpc_lds_bytes", "mmpc_problems_per_cu", "mmpc_set_warm_start", "mmpc_set_schedule_hint", "mmpc_set_iteration_budget", "mmpc_resume_batch_device", "mmpc_solve_list_device", "mmpc_suspended_count", "mmpc_last_error", "mmpc_version", "mmpc_ik_batch", "mmpc_ik_batch_device",
-           "mmpc_tick_prepare_device"]
+           "mmpc_tick_prepare_device", "mmpc_set_obstacle_clock"]
 
 _lib = None
 _dp = C.POINTER(C.c_double)
@@ -70,6 +70,7 @@ def lib():
         L.mmpc_ik_batch.argtypes = [C.c_int, C.c_int, _dp, _dp, _dp, _ip, _ip]
         L.mmpc_ik_batch_device.argtypes = [C.c_int, C.c_int] + [C.c_void_p] * 5 + [C.c_void_p]
         L.mmpc_tick_prepare_device.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 8 + [C.c_void_p]
+        L.mmpc_set_obstacle_clock.argtypes = [C.c_void_p, C.c_void_p]
         _lib = L
     return _lib
 
@@ -105,9 +106,13 @@ class Engine:
         self.kind, self.N, self.M = kind, int(N), int(M)
         self.nx, self.nu = (6, 2) if kind == KIND_BASE else (9, 5)
         self.nref = 4 if kind == KIND_WHOLEBODY_POSE else self.nx      # reference row: endpoint pose (x,y,z,psi) or the state
-        self.max_batch, self.device, self.obs_per_stage = int(max_batch), int(device), bool(obs_per_stage)
+        # obs_per_stage: False (static record), True (table per stage), "motion" (record with velocities + clock); an int is
+        # handed to mmpc_create as it is (which refuses anything but 0, 1, 2)
+        self.max_batch, self.device = int(max_batch), int(device)
+        self.obs_mode = 2 if obs_per_stage == "motion" else int(obs_per_stage)
+        self.obs_per_stage = "motion" if self.obs_mode == 2 else bool(self.obs_mode)
         cfg = MmpcConfig()
-        cfg.kind, cfg.N, cfg.M, cfg.obs_per_stage = kind, self.N, self.M, int(self.obs_per_stage)
+        cfg.kind, cfg.N, cfg.M, cfg.obs_per_stage = kind, self.N, self.M, self.obs_mode
         cfg.max_batch, cfg.device, cfg.max_iter = self.max_batch, self.device, int(max_iter)
         cfg.dt, cfg.tol, cfg.mu_init = float(dt), float(tol), float(mu_init)
         ulim = np.asarray(ulim, float); xlim = np.asarray(xlim, float); dulim = np.asarray(dulim, float)
@@ -183,6 +188,18 @@ class Engine:
         self._chk(lib().mmpc_set_warm_start(self._h, C.c_void_p(u_guess.data_ptr()) if u_guess is not None else None,
                                             float(mu_init)), "mmpc_set_warm_start")
 
+    def set_obstacle_clock(self, tick=None):
+        """mmpc_set_obstacle_clock (motion handles): `tick` (max_batch,) cuda int64 tensor of per-instance tick counts (kept alive
+        by the engine, read by the kernels at launch time) or None (tick 0 for every instance)."""
+        if tick is not None:
+            import torch
+            if (not tick.is_cuda or tick.dtype != torch.int64 or not tick.is_contiguous() or tick.device.index != self.device
+                    or tuple(tick.shape) != (self.max_batch,)):
+                raise ValueError("tick must be a contiguous cuda:%d int64 tensor (max_batch,) = (%d,)" % (self.device, self.max_batch))
+        self._chk(lib().mmpc_set_obstacle_clock(self._h, C.c_void_p(tick.data_ptr()) if tick is not None else None),
+                  "mmpc_set_obstacle_clock")
+        self._tick = tick
+
     def set_schedule_hint(self, mode):
         """mmpc_set_schedule_hint: launch order of a batch's workgroups - 0/False batch order, 1/True (default) longest-first
         by the previous launch's iteration counts when there is one, else by the a-priori difficulty key of the batch's own
@@ -206,6 +223,8 @@ class Engine:
         self._chk(lib().mmpc_reset(self._h), "mmpc_reset")
 
     def obs_shape(self, B):
+        if self.obs_mode == 2:
+            return (B, self.M, 5)
         return (B, self.N + 1, self.M, 3) if self.obs_per_stage else (B, self.M, 3)
 
     def solve_batch(self, x_init, traj_ref, u_ref, obs):

@@ -120,7 +120,8 @@ class MPCWholeBody:
 
     # ---- batched extension -------------------------------------------------------------
     def solve_batch(self, x_init, traj_ref, u_ref, obs=None):
-        """B independent instances of solve(); obs (B,M,3) [or (B,N+1,M,3)] overrides obstacle_list.
+        """B independent instances of solve(); obs (B,M,3) [or (B,N+1,M,3) with obs_per_stage=True, or the motion record
+        (B,M,5) = (x, y, radius, v_x, v_y) with obs_per_stage="motion"] overrides obstacle_list.
         Returns dict(u0,X,U,s,status,iters,cost); the warm start of instance b is kept for the next call."""
         x_init = np.array(x_init, float)
         x_init = np.maximum(np.minimum(x_init, self.xlim[1]), self.xlim[0])

@@ -230,7 +230,8 @@ MMPC_HD constexpr MmpcLayout mmpc_layout(int N, int M, int obs_per_stage, int nh
 #define MMPC_CARVE(name, n) L.name = o; o += (n); o = (o + 1) & ~1;
     MMPC_CARVE(X, NS * D::NX) MMPC_CARVE(U, N * D::NU) MMPC_CARVE(S, NS) MMPC_CARVE(LAM, NS * D::NX)
     MMPC_CARVE(XREF, NS * D::NX) MMPC_CARVE(UREF, N * D::NU) MMPC_CARVE(ULAST, N * D::NU)
-    MMPC_CARVE(OBS, (obs_per_stage ? NS : 1) * M * 3)
+    // obstacles: the static record M x 3, the per-stage table (N + 1) x M x 3, or the motion record M x 5 + the instance's tick (mode 2)
+    MMPC_CARVE(OBS, obs_per_stage == 2 ? M * 5 + 1 : (obs_per_stage ? NS : 1) * M * 3)
     MMPC_CARVE(T, NS * L.R) MMPC_CARVE(Z, NS * L.R) MMPC_CARVE(HR, NS * L.NR) MMPC_CARVE(DTR, NS * L.NR)
     MMPC_CARVE(GC, NS * M * 2) MMPC_CARVE(HC, NS * M * 3) MMPC_CARVE(GSF, NS * D::NSELF * 6)
     MMPC_CARVE(CV, NS * MMPC_NCV) MMPC_CARVE(CD, NS * D::NX) MMPC_CARVE(GX, NS * D::NX) MMPC_CARVE(GU, NS * D::NU)
@@ -269,6 +270,7 @@ struct MmpcIO {
     int budget, resume;
     double *gscr;      // this instance's gain block in global memory (specialised kernels of long horizons, MmpcGainBlock), else unused
     double *soc;       // this instance's scratch of the second-order correction in global memory (mmpc_soc_doubles; null: no corrections)
+    const long long *tick;   // obs_per_stage = 2: this instance's tick count (null: 0), mmpc_set_obstacle_clock
 };
 // doubles of an instance's second-order-correction scratch (both kernels; NR = rows per stage that are not box rows): the
 // uncorrected direction, and for the specialised kernels - which move to a trial point in place - the constraint residuals of the
@@ -276,7 +278,7 @@ struct MmpcIO {
 MMPC_HD constexpr int mmpc_soc_doubles(int N, int NX, int NU, int NR) { return (N + 1) * (4 * NX + NU + 1 + 2 * NR) + 8; }
 // Instance b of a batch: the one place where the batch's pointers become an instance's slices (every solve kernel and both
 // runners of the host emulation).  so = doubles of an instance's obstacle table; soc_stride = doubles of its correction scratch.
-// The budget fields are the specialised kernels' own: they set them after the call.  (Filled in place: returned by value the
+// The budget fields are the specialised kernels' own, the tick is the motion mode's: the kernel wrappers set them after the call.  (Filled in place: returned by value the
 // struct travels through a noalias return slot, whose scopes on every access here change the kernels' code.)
 template <int KIND>
 MMPC_DEV void mmpc_instance_io(MmpcIO &io, const MmpcParams &P, int b, int N, size_t so, const double *x_init,
@@ -298,8 +300,39 @@ MMPC_DEV void mmpc_instance_io(MmpcIO &io, const MmpcParams &P, int b, int N, si
     io.iters = iters + b;
     io.cost = cost + b;
     io.err = err + b;
-    io.state = nullptr; io.budget = 0; io.resume = 0; io.gscr = nullptr;
+    io.state = nullptr; io.budget = 0; io.resume = 0; io.gscr = nullptr; io.tick = nullptr;
     io.soc = soc ? soc + (size_t)b * soc_stride : nullptr;
+}
+
+// ---- moving obstacles (the fleet tick's table, mmpc_tick.h, and the motion record of obs_per_stage = 2): centre of an obstacle at
+// time t, c + v t, and the time of stage k, (tick + k) dt - every operation rounded on its own (no fused multiply-add: hipcc
+// contracts a * b + c by default; a host build passes -ffp-contract=off)
+MMPC_DEV double mmpc_tick_centre(double c, double v, double t) {
+#pragma clang fp contract(off)
+    return c + v * t;
+}
+MMPC_DEV double mmpc_tick_time(long long tick, int k, double dt) {
+#pragma clang fp contract(off)
+    return (double)(tick + k) * dt;
+}
+// the same from the tick as a double: (double)tick + (double)k is (double)(tick + k) exactly for 0 <= tick < 2^52
+MMPC_DEV double mmpc_tick_time_d(double tickd, int k, double dt) {
+#pragma clang fp contract(off)
+    return (tickd + (double)k) * dt;
+}
+// An obstacle as the rows read it - what the kernels' one accessor (obs_ptr) hands back: the values x(), y(), r(), each formed where
+// it is read.  (Not a struct of three doubles loaded up front: that order of loads alone moved mmpc_fast_kernel<0,20,3> with a
+// table from 470 to 473 registers.)  p: the obstacle's words - (x, y, r) of the static record or of the table's stage, or
+// (c_x, c_y, r, v_x, v_y) of the motion record with t the time of the stage.
+struct MmpcObs {
+    const double *p; double t; bool motion;
+    MMPC_DEV double x() const { return motion ? mmpc_tick_centre(p[0], p[3], t) : p[0]; }
+    MMPC_DEV double y() const { return motion ? mmpc_tick_centre(p[1], p[4], t) : p[1]; }
+    MMPC_DEV double r() const { return p[2]; }
+};
+// obstacle m of the motion record `rec` (M x 5; word 5 M: the instance's tick as a double) at stage k
+MMPC_DEV MmpcObs mmpc_obs_motion(const double *rec, int M, int k, int m, double dt) {
+    return MmpcObs{rec + m * 5, mmpc_tick_time_d(rec[M * 5], k, dt), true};
 }
 
 MMPC_DEV double mmpc_min(double a, double b) { return a < b ? a : b; }
@@ -618,6 +651,13 @@ MMPC_DEV void mmpc_solve_one(const MmpcParams &P, const MmpcIO io, double *lds M
     constexpr int NX = D::NX, NU = D::NU, NSELF = D::NSELF, NV = D::NV, NXX = D::NXX, NUU = D::NUU;
     const int N = NC ? NC : P.N, M = MC >= 0 ? MC : P.M, NS = N + 1;
     const int OPS = OPSC >= 0 ? OPSC : P.obs_per_stage, PL = LC >= 0 ? LC : P.L;
+    // motion record (obs_per_stage = 2): a constant of every device instantiation (the run-time-sized kernel has one of its own for
+    // the mode, mmpc_hip.hip: the kernels of modes 0 and 1 carry none of its code); the host emulation reads the mode from P
+#ifdef MMPC_EMU
+    const bool MOTION = OPS == 2;
+#else
+    constexpr bool MOTION = OPSC == 2;
+#endif
     const int NHS = (KIND == 0 && PL > 0) ? 6 : 0;
     const int NQ = (KIND == 0 && (AWC >= 0 ? AWC : P.as_written) && PL >= 2) ? 6 * (PL - 1) : 0;   // rows of the NLP as written (quirk Q8), stages >= 1
     constexpr int NREF = D::NREF;
@@ -657,8 +697,10 @@ MMPC_DEV void mmpc_solve_one(const MmpcParams &P, const MmpcIO io, double *lds M
         }
         return mmpc_bound_active(b);
     };
-    auto obs_ptr = [&](int k, int m) -> const double * {
-        return OBS + ((OPS ? k * M : 0) + m) * 3;
+    // the one accessor of an obstacle: values through MmpcObs, not a pointer (mode 2 forms the centre from the record and the instance's tick)
+    auto obs_ptr = [&](int k, int m) -> MmpcObs {
+        if (MOTION) return mmpc_obs_motion(OBS, M, k, m, dt);
+        return MmpcObs{OBS + ((OPS ? k * M : 0) + m) * 3, 0.0, false};
     };
     auto slack_idx = [&](int k) -> int { return k < N - 1 ? k : N - 1; };  // :265 quirk (Q1)
     // row e = i (L-1) + j of the NLP as written at stage k >= 1: min(-max_{j' <= j} c_{k,i,j'}, -max_{j' > j} c_{k-1,i,j'}) (without
@@ -709,6 +751,10 @@ MMPC_DEV void mmpc_solve_one(const MmpcParams &P, const MmpcIO io, double *lds M
     for (int i = lane; i < NS; i += MMPC_WAVE) S[i] = 0.0;  // :304
     if (lane < 4) NUEQ[lane] = 0.0;
     if (lane < 16) SIGW[lane] = 0.0;
+    if (MOTION) {
+        for (int i = lane; i < M * 5; i += MMPC_WAVE) OBS[i] = io.obs[i];
+        if (lane == 0) OBS[M * 5] = io.tick ? (double)io.tick[0] : 0.0;
+    } else
     for (int i = lane; i < (OPS ? NS : 1) * M * 3; i += MMPC_WAVE) OBS[i] = io.obs[i];
     LANES_END
     // bound push of the initial point (needs U_last of the previous phase for the merged input box)
@@ -733,9 +779,9 @@ MMPC_DEV void mmpc_solve_one(const MmpcParams &P, const MmpcIO io, double *lds M
     // returns via hr[NR]
     auto nl_rows = [&](int k, const double *xk, double sk, double sks, double *hr) {
         for (int m = 0; m < M; m++) {
-            const double *o = obs_ptr(k, m);
-            const double dx = xk[0] - o[0], dy = xk[1] - o[1];
-            hr[m] = (o[2] + MMPC_BASE_R) - sqrt(dx * dx + dy * dy) - sk;  // mpc_wholebody_qref.py:53
+            const MmpcObs o = obs_ptr(k, m);
+            const double dx = xk[0] - o.x(), dy = xk[1] - o.y();
+            hr[m] = (o.r() + MMPC_BASE_R) - sqrt(dx * dx + dy * dy) - sk;  // mpc_wholebody_qref.py:53
         }
         if (NSELF) {
             double dr[3], dz[3], sn, cs;
@@ -993,10 +1039,10 @@ MMPC_DEV void mmpc_solve_one(const MmpcParams &P, const MmpcIO io, double *lds M
             // circle rows: value, gradient, Hessian (mpc_wholebody_qref.py:49-54)
             double rds = 2 * Sw * S[k], selfz = 0.0;
             for (int m = 0; m < M; m++) {
-                const double *o = obs_ptr(k, m);
-                const double dx = xk[0] - o[0], dy = xk[1] - o[1], d = sqrt(dx * dx + dy * dy), id = 1.0 / d;
+                const MmpcObs o = obs_ptr(k, m);
+                const double dx = xk[0] - o.x(), dy = xk[1] - o.y(), d = sqrt(dx * dx + dy * dy), id = 1.0 / d;
                 const double nxv = dx * id, nyv = dy * id;
-                const double h = (o[2] + MMPC_BASE_R) - d - S[k];
+                const double h = (o.r() + MMPC_BASE_R) - d - S[k];
                 HR[k * NR + m] = h;
                 GC[(k * M + m) * 2 + 0] = -nxv; GC[(k * M + m) * 2 + 1] = -nyv;
                 HC[(k * M + m) * 3 + 0] = -(1 - nxv * nxv) * id; HC[(k * M + m) * 3 + 1] = nxv * nyv * id;
@@ -1867,9 +1913,9 @@ MMPC_DEV void mmpc_solve_one(const MmpcParams &P, const MmpcIO io, double *lds M
             double hr[HRMAX];
             {
                 for (int m = 0; m < M; m++) {
-                    const double *o = obs_ptr(k, m);
-                    const double dx = xk[0] - o[0], dy = xk[1] - o[1];
-                    hr[m] = (o[2] + MMPC_BASE_R) - sqrt(dx * dx + dy * dy) - sk;
+                    const MmpcObs o = obs_ptr(k, m);
+                    const double dx = xk[0] - o.x(), dy = xk[1] - o.y();
+                    hr[m] = (o.r() + MMPC_BASE_R) - sqrt(dx * dx + dy * dy) - sk;
                 }
                 if (NSELF) {
                     double dr[3], dz[3];

@@ -216,7 +216,9 @@ MMPC_HD constexpr MmpcFastLayout mmpc_fast_layout(int M, int obs_per_stage) {
 #define MMPC_CARVE(name, n) L.name = o; o += (n); o = (o + 1) & ~1;
     MMPC_CARVE(XU, F::NS * F::NV) MMPC_CARVE(S, F::NS) MMPC_CARVE(LAM, F::NS * F::NX)
     MMPC_CARVE(XUREF, SLIM ? 0 : F::NS * F::NV) MMPC_CARVE(ULAST, SLIM ? 0 : F::NS * F::NU)
-    MMPC_CARVE(OBS, obs_per_stage ? (SLIM ? 0 : F::NS * M * 3) : M * 3)
+    // obstacles: the static record, the per-stage table (long horizons leave it in HBM/L2), or the motion record M x 5 + the
+    // instance's tick (mode 2: in LDS at every horizon)
+    MMPC_CARVE(OBS, obs_per_stage == 2 ? M * 5 + 1 : (obs_per_stage ? (SLIM ? 0 : F::NS * M * 3) : M * 3))
     MMPC_CARVE(CST, MMPC_C_SIZE) MMPC_CARVE(CV, F::NS * MMPC_NCV) MMPC_CARVE(CD, F::NS * F::NX) MMPC_CARVE(TRG, F::NS * F::TRGS)
     MMPC_CARVE(HXX, F::NS * F::NXX) MMPC_CARVE(QXU, F::NS * F::NV) MMPC_CARVE(HUXL, F::NU * F::NX)
     MMPC_CARVE(HUUL, F::NUU) MMPC_CARVE(HUX02, F::NS) MMPC_CARVE(HUUD, F::NS * F::NU) MMPC_CARVE(SN, 16)
@@ -424,8 +426,13 @@ MMPC_DEV void mmpc_solve_fast(const MmpcParams &P, const MmpcIO io, double *lds 
     MmpcLaneState<KIND, N, MC> ls_one;
     double wr_one[9];
 #endif
-    const double *const OBSP = (SLIM && ops) ? io.obs : OBS;
-    auto obs_ptr = [&](int k, int m) -> const double * { return OBSP + ((ops ? k * M : 0) + m) * 3; };
+    const double *const OBSP = (SLIM && ops == 1) ? io.obs : OBS;
+    // the one accessor of an obstacle: values through MmpcObs (mmpc_core.h), not a pointer.  Motion mode (ops = 2) forms the centre from the record in LDS and the
+    // instance's tick where it is read (two multiplies, two adds; nothing of it is kept across phases)
+    auto obs_ptr = [&](int k, int m) -> MmpcObs {
+        if (ops == 2) return mmpc_obs_motion(OBS, M, k, m, dt);
+        return MmpcObs{OBSP + ((ops ? k * M : 0) + m) * 3, 0.0, false};
+    };
     auto ulast_at = [&](int k, int a) -> double {
         if (!SLIM) return ULAST[k * NU + a];
         return k < N ? io.u_last[k * NU + a] : 0.0;
@@ -457,7 +464,10 @@ MMPC_DEV void mmpc_solve_fast(const MmpcParams &P, const MmpcIO io, double *lds 
         for (int i = lane; i < NS * NU; i += MMPC_WAVE) ULAST[i] = i < N * NU ? io.u_last[i] : 0.0;
     for (int i = lane; i < NS * NX; i += MMPC_WAVE) LAM[i] = 0.0;
     for (int i = lane; i < NS; i += MMPC_WAVE) S[i] = 0.0;
-    if (!(SLIM && ops))
+    if (ops == 2) {
+        for (int i = lane; i < M * 5; i += MMPC_WAVE) OBS[i] = io.obs[i];
+        if (lane == 0) OBS[M * 5] = io.tick ? (double)io.tick[0] : 0.0;
+    } else if (!(SLIM && ops))
         for (int i = lane; i < (ops ? NS : 1) * M * 3; i += MMPC_WAVE) OBS[i] = io.obs[i];
     for (int i = lane; i < MMPC_C_SIZE; i += MMPC_WAVE) {
         double v = 0.0;
@@ -649,9 +659,9 @@ MMPC_DEV void mmpc_solve_fast(const MmpcParams &P, const MmpcIO io, double *lds 
             for (int r = 0; r < MCR; r++) {
                 const int m = rs + RG * r;
                 if (m < M) {
-                    const double *o = obs_ptr(rk, m);
-                    const double dx = px - o[0], dy = py - o[1];
-                    const double h = (o[2] + MMPC_BASE_R) - sqrt(dx * dx + dy * dy) - sk;
+                    const MmpcObs o = obs_ptr(rk, m);
+                    const double dx = px - o.x(), dy = py - o.y();
+                    const double h = (o.r() + MMPC_BASE_R) - sqrt(dx * dx + dy * dy) - sk;
                     ls.ct[r] = mmpc_vmax(-h, 1e-2); ls.cz[r] = mu / ls.ct[r];
                 }
             }
@@ -867,9 +877,9 @@ MMPC_DEV void mmpc_solve_fast(const MmpcParams &P, const MmpcIO io, double *lds 
                 for (int r = 0; r < MCR; r++) {
                     const int m = rs + RG * r;
                     if (m < M) {
-                        const double *o = obs_ptr(rk, m);
-                        const double dx = px - o[0], dy = py - o[1];
-                        const double rr = (o[2] + MMPC_BASE_R) - sqrt(dx * dx + dy * dy) - sk + ls.ct[r];
+                        const MmpcObs o = obs_ptr(rk, m);
+                        const double dx = px - o.x(), dy = py - o.y();
+                        const double rr = (o.r() + MMPC_BASE_R) - sqrt(dx * dx + dy * dy) - sk + ls.ct[r];
                         const int e = rk * NRS + m;
                         if (!acc) tr[e] = rr; else ar[e] = a_prev * (first ? rr : ar[e]) + tr[e];
                     }

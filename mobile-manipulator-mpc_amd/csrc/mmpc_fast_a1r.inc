@@ -11,8 +11,8 @@
                     double ob[MCR * 3];
 #pragma unroll
                     for (int r = 0; r < MCR; r++) {
-                        const double *o = obs_ptr(rk, rs + RG * r < M ? rs + RG * r : 0);
-                        ob[3 * r] = o[0]; ob[3 * r + 1] = o[1]; ob[3 * r + 2] = o[2];
+                        const MmpcObs o = obs_ptr(rk, rs + RG * r < M ? rs + RG * r : 0);
+                        ob[3 * r] = o.x(); ob[3 * r + 1] = o.y(); ob[3 * r + 2] = o.r();
                     }
 #pragma unroll
                     for (int r = 0; r < MCR; r++) {

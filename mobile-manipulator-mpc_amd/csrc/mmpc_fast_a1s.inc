@@ -17,7 +17,7 @@
                     for (int q = 0; q < (RG - 1) * 9; q++) ob[q] = M > 0 ? HXX[MMPC_MUL24(k, NXX) + q] : 0.0;
                 } else {
 #pragma unroll
-                    for (int m = 0; m < M; m++) { const double *o = obs_ptr(k, m); ob[3 * m] = o[0]; ob[3 * m + 1] = o[1]; ob[3 * m + 2] = o[2]; }
+                    for (int m = 0; m < M; m++) { const MmpcObs o = obs_ptr(k, m); ob[3 * m] = o.x(); ob[3 * m + 1] = o.y(); ob[3 * m + 2] = o.r(); }
                 }
                 double sn = 0.0, cs = 0.0, dr[3] = {0, 0, 0}, dz[3] = {0, 0, 0};
                 if (NSELF) {

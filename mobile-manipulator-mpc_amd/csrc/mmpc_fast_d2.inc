@@ -24,8 +24,8 @@
                 double ob[MCR * 3];
 #pragma unroll
                 for (int r = 0; r < MCR; r++) {
-                    const double *o = obs_ptr(rk, rs + RG * r < M ? rs + RG * r : 0);
-                    ob[3 * r] = o[0]; ob[3 * r + 1] = o[1]; ob[3 * r + 2] = o[2];
+                    const MmpcObs o = obs_ptr(rk, rs + RG * r < M ? rs + RG * r : 0);
+                    ob[3 * r] = o.x(); ob[3 * r + 1] = o.y(); ob[3 * r + 2] = o.r();
                 }
 #pragma unroll
                 for (int r = 0; r < MCR; r++) {
@@ -50,7 +50,7 @@
             const double px = XU[MMPC_MUL24(k, NV)], py = XU[MMPC_MUL24(k, NV) + 1], sk = S[k];
             double ob[(MC > 0 ? MC : 1) * 3];
 #pragma unroll
-            for (int m = 0; m < (RG > 1 ? 0 : M); m++) { const double *o = obs_ptr(k, m); ob[3 * m] = o[0]; ob[3 * m + 1] = o[1]; ob[3 * m + 2] = o[2]; }
+            for (int m = 0; m < (RG > 1 ? 0 : M); m++) { const MmpcObs o = obs_ptr(k, m); ob[3 * m] = o.x(); ob[3 * m + 1] = o.y(); ob[3 * m + 2] = o.r(); }
 #pragma unroll
             for (int m = 0; m < (RG > 1 ? 0 : M); m++) {
                 const double ddx = px - ob[3 * m], ddy = py - ob[3 * m + 1], m2 = ddx * ddx + ddy * ddy, id = mmpc_rsqrt(m2), d = m2 * id;

@@ -19,8 +19,8 @@
                 double ob[MCR * 3];
 #pragma unroll
                 for (int r = 0; r < MCR; r++) {
-                    const double *o = obs_ptr(rk, rs + RG * r < M ? rs + RG * r : 0);
-                    ob[3 * r] = o[0]; ob[3 * r + 1] = o[1]; ob[3 * r + 2] = o[2];
+                    const MmpcObs o = obs_ptr(rk, rs + RG * r < M ? rs + RG * r : 0);
+                    ob[3 * r] = o.x(); ob[3 * r + 1] = o.y(); ob[3 * r + 2] = o.r();
                 }
 #pragma unroll
                 for (int r = 0; r < MCR; r++) {
@@ -63,7 +63,7 @@
                 for (int q = 0; q < (RG - 1) * 3; q++) ob[q] = M > 0 ? HXX[MMPC_MUL24(k, NXX) + q] : 0.0;
             } else {
 #pragma unroll
-                for (int m = 0; m < M; m++) { const double *o = obs_ptr(k, m); ob[3 * m] = o[0]; ob[3 * m + 1] = o[1]; ob[3 * m + 2] = o[2]; }
+                for (int m = 0; m < M; m++) { const MmpcObs o = obs_ptr(k, m); ob[3 * m] = o.x(); ob[3 * m + 1] = o.y(); ob[3 * m + 2] = o.r(); }
             }
             const double sk = S[k], sks_ld = S[slack_idx(k)];
             double sn, cs;

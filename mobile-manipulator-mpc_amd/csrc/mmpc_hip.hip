@@ -22,17 +22,19 @@ __global__ __launch_bounds__(MMPC_WAVE) void mmpc_solve_kernel(
     const double *__restrict__ u_ref, const double *__restrict__ u_last, const double *__restrict__ x_guess,
     const double *__restrict__ obs, double *__restrict__ X, double *__restrict__ U, double *__restrict__ s,
     int *__restrict__ status, int *__restrict__ iters, double *__restrict__ cost, double *__restrict__ err,
-    const int *__restrict__ order, double *__restrict__ soc, int soc_stride) {
+    const int *__restrict__ order, double *__restrict__ soc, int soc_stride, const long long *__restrict__ tick) {
     extern __shared__ double lds[];
     if ((int)blockIdx.x >= B) return;
     // longest-first schedule hint: workgroup i solves instance order[i] (a permutation; results do not depend on it)
     const int b = order ? order[blockIdx.x] : (int)blockIdx.x;
     const MmpcParams &P = *Pp;
     const int N = NC ? NC : P.N, M = MC >= 0 ? MC : P.M;
-    const size_t so = (size_t)((OPSC >= 0 ? OPSC : P.obs_per_stage) ? N + 1 : 1) * M * 3;
+    // (doubles of an instance's obstacles: the motion record of OPSC = 2 - a constant of the instantiation, see mmpc_solve_one - or the table)
+    const size_t so = OPSC == 2 ? (size_t)M * 5 : (size_t)((OPSC >= 0 ? OPSC : P.obs_per_stage) ? N + 1 : 1) * M * 3;
     MmpcIO io;
     mmpc_instance_io<KIND>(io, P, b, N, so, x_init, traj_ref, u_ref, u_last, x_guess, obs, X, U, s, status, iters, cost, err,
                            soc, soc_stride);
+    if (OPSC == 2 && tick) io.tick = tick + b;
     mmpc_solve_one<KIND, NC, MC, OPSC, LC>(P, io, lds);
 }
 
@@ -45,17 +47,18 @@ __global__ __launch_bounds__(MMPC_WAVE) void mmpc_solve_kernel_static(
     const double *__restrict__ u_ref, const double *__restrict__ u_last, const double *__restrict__ x_guess,
     const double *__restrict__ obs, double *__restrict__ X, double *__restrict__ U, double *__restrict__ s,
     int *__restrict__ status, int *__restrict__ iters, double *__restrict__ cost, double *__restrict__ err,
-    const int *__restrict__ order, double *__restrict__ soc, int soc_stride) {
+    const int *__restrict__ order, double *__restrict__ soc, int soc_stride, const long long *__restrict__ tick) {
     constexpr int NHS = (KIND == 0 && LC > 0) ? 6 : 0, NQ = (KIND == 0 && AWC && LC >= 2) ? 6 * (LC - 1) : 0;
     __shared__ double lds[mmpc_layout<KIND>(NC, MC, OPSC, NHS, NQ).total];
     if ((int)blockIdx.x >= B) return;
     const int b = order ? order[blockIdx.x] : (int)blockIdx.x;
     const MmpcParams &P = *Pp;
     constexpr int N = NC, M = MC;
-    constexpr size_t so = (size_t)(OPSC ? N + 1 : 1) * M * 3;
+    constexpr size_t so = OPSC == 2 ? (size_t)M * 5 : (size_t)(OPSC ? N + 1 : 1) * M * 3;
     MmpcIO io;
     mmpc_instance_io<KIND>(io, P, b, N, so, x_init, traj_ref, u_ref, u_last, x_guess, obs, X, U, s, status, iters, cost, err,
                            soc, soc_stride);
+    if (OPSC == 2 && tick) io.tick = tick + b;
     mmpc_solve_one<KIND, NC, MC, OPSC, LC, AWC>(P, io, lds);
 }
 // (kind, N, M, obs_per_stage, L, as_written): demo_wholebody_qref.py scenario 2 (two planes) as written and with the intended
@@ -66,7 +69,7 @@ __global__ __launch_bounds__(MMPC_WAVE) void mmpc_solve_kernel_static(
 #define MMPC_STATIC_LIST(X) X(0, 20, 3, 0, 2, 1) X(0, 20, 3, 0, 2, 0) X(0, 20, 3, 0, 3, 1) X(0, 20, 3, 0, 0, 0) X(0, 20, 5, 0, 0, 0)
 #endif
 
-// OPS = obstacle table per stage (config obs_per_stage): part of the LDS layout.  The LDS block is STATIC (its size is a
+// OPS = the config's obs_per_stage (0 static record, 1 table per stage, 2 motion record + clock): part of the LDS layout.  The LDS block is STATIC (its size is a
 // constant of the instantiation): with `extern __shared__` the base of the dynamic block is resolved after instruction
 // selection and every lane-derived LDS address carries an add of that constant 0 (14 of the ~200 instructions of a Riccati stage).
 template <int KIND, int N, int MC, int WPE, bool CONT, int OPS>
@@ -76,7 +79,8 @@ __global__ __launch_bounds__(MMPC_WAVE, WPE) void mmpc_fast_kernel(
     const double *__restrict__ obs, double *__restrict__ X, double *__restrict__ U, double *__restrict__ s,
     int *__restrict__ status, int *__restrict__ iters, double *__restrict__ cost, double *__restrict__ err,
     const int *__restrict__ order, int budget, double *__restrict__ state, int state_stride, const int *__restrict__ resume_count,
-    const int *__restrict__ list_count, double *__restrict__ gscr, double *__restrict__ soc, int soc_stride) {
+    const int *__restrict__ list_count, double *__restrict__ gscr, double *__restrict__ soc, int soc_stride,
+    const long long *__restrict__ tick) {
     __shared__ double lds[mmpc_fast_layout<KIND, N>(MC, OPS).total];
     // A continuation launch (resume_count != null): `order` is the compacted list of the suspended instances, *resume_count its
     // length, and the grid is SMALL (MMPC_RESUME_GRID workgroups that stride over the list): a handful of instances is left,
@@ -93,7 +97,7 @@ __global__ __launch_bounds__(MMPC_WAVE, WPE) void mmpc_fast_kernel(
         if ((unsigned)b >= (unsigned)B) { if (!CONT || !resume_count) break; continue; }
         const MmpcParams &P = *Pp;
         const int M = MC;
-        const size_t so = (size_t)(P.obs_per_stage ? N + 1 : 1) * M * 3;
+        const size_t so = OPS == 2 ? (size_t)M * 5 : (size_t)(P.obs_per_stage ? N + 1 : 1) * M * 3;
         MmpcIO io;
         mmpc_instance_io<KIND>(io, P, b, N, so, x_init, traj_ref, u_ref, u_last, x_guess, obs, X, U, s, status, iters, cost, err,
                                soc, soc_stride);
@@ -101,6 +105,7 @@ __global__ __launch_bounds__(MMPC_WAVE, WPE) void mmpc_fast_kernel(
         io.budget = budget;
         io.resume = resume_count ? 1 : 0;
         io.gscr = MmpcGainBlock<KIND, N>::ON ? gscr + (size_t)b * MmpcGainBlock<KIND, N>::total : nullptr;
+        if (OPS == 2 && tick) io.tick = tick + b;   // the clock is indexed by instance row, like every per-instance array
         mmpc_solve_fast<KIND, N, MC, CONT, OPS>(P, io, lds);
         if (!CONT || !resume_count) break;      // (one instance per workgroup except in a continuation launch)
         __builtin_amdgcn_s_barrier();           // the next instance reuses the LDS block
@@ -160,10 +165,13 @@ __global__ __launch_bounds__(256) void mmpc_collect_suspended_list(int B, const 
 // is the key.  On the demo's shape (2048 starts around the two planes, list-scheduled on 256 slots: 372 iterations of wall time
 // in batch order, 250 exact) it gives 258 for the rows as written and 256 for the intended rows (exact there: 219) - the
 // circles of that scenario are far away and their key alone is batch order.
-__global__ __launch_bounds__(64) void mmpc_difficulty_key(int B, int N, int M, int nref, int obs_per_stage,
+// MOTION: `obs` is the motion record of obs_per_stage = 2 and `tick` its clock (null: 0) - the centres are those of the table twin,
+// formed by the same helpers (mmpc_core.h), and so is the key.
+template <bool MOTION>
+__device__ __forceinline__ void mmpc_difficulty_key_body(int B, int N, int M, int nref, int obs_per_stage,
                                                           const double *__restrict__ traj_ref, const double *__restrict__ obs,
                                                           int *__restrict__ key, const MmpcParams *__restrict__ Pp,
-                                                          const double *__restrict__ x_init, int planes) {
+                                                          const double *__restrict__ x_init, int planes, const long long *__restrict__ tick) {
     const int b = blockIdx.x * 64 + threadIdx.x;
     if (b >= B) return;
     int key_hs = 0;
@@ -178,8 +186,19 @@ __global__ __launch_bounds__(64) void mmpc_difficulty_key(int B, int N, int M, i
         key_hs = (int)fmin(fmax(q2, 0.0), 255.0);   // (a NaN start: 0 - the solve reports it)
     }
     const double *tr = traj_ref + (size_t)b * (N + 1) * nref;
-    const double *ob = obs + (size_t)b * (obs_per_stage ? N + 1 : 1) * M * 3;
     double worst = -1.0e9;
+    if constexpr (MOTION) {
+        const double *rec = obs + (size_t)b * M * 5;
+        const double tickd = tick ? (double)tick[b] : 0.0, dt = Pp->dt;
+        for (int k = 0; k <= N; k++) {
+            const double x = tr[k * nref], y = tr[k * nref + 1], t = mmpc_tick_time_d(tickd, k, dt);
+            for (int m = 0; m < M; m++) {
+                const double dx = x - mmpc_tick_centre(rec[5 * m], rec[5 * m + 3], t), dy = y - mmpc_tick_centre(rec[5 * m + 1], rec[5 * m + 4], t);
+                worst = fmax(worst, (rec[5 * m + 2] + MMPC_BASE_R) - sqrt(dx * dx + dy * dy));
+            }
+        }
+    } else {
+    const double *ob = obs + (size_t)b * (obs_per_stage ? N + 1 : 1) * M * 3;
     for (int k = 0; k <= N; k++) {
         const double x = tr[k * nref], y = tr[k * nref + 1];
         const double *o = ob + (obs_per_stage ? (size_t)k * M * 3 : 0);
@@ -188,10 +207,23 @@ __global__ __launch_bounds__(64) void mmpc_difficulty_key(int B, int N, int M, i
             worst = fmax(worst, (o[3 * m + 2] + MMPC_BASE_R) - sqrt(dx * dx + dy * dy));
         }
     }
+    }
     // [-1.5 m clearance .. 1.0 m penetration] -> 0..255
     const double q = (worst + 1.5) * (255.0 / 2.5);
     const int key_c = M > 0 ? (int)fmin(fmax(q, 0.0), 255.0) : 0;
     key[b] = key_c > key_hs ? key_c : key_hs;
+}
+__global__ __launch_bounds__(64) void mmpc_difficulty_key(int B, int N, int M, int nref, int obs_per_stage,
+                                                          const double *__restrict__ traj_ref, const double *__restrict__ obs,
+                                                          int *__restrict__ key, const MmpcParams *__restrict__ Pp,
+                                                          const double *__restrict__ x_init, int planes) {
+    mmpc_difficulty_key_body<false>(B, N, M, nref, obs_per_stage, traj_ref, obs, key, Pp, x_init, planes, nullptr);
+}
+__global__ __launch_bounds__(64) void mmpc_difficulty_key_motion(int B, int N, int M, int nref, const double *__restrict__ traj_ref,
+                                                                 const double *__restrict__ rec, int *__restrict__ key,
+                                                                 const MmpcParams *__restrict__ Pp, const double *__restrict__ x_init,
+                                                                 int planes, const long long *__restrict__ tick) {
+    mmpc_difficulty_key_body<true>(B, N, M, nref, 2, traj_ref, rec, key, Pp, x_init, planes, tick);
 }
 
 // out_u0[b][a] = U[b][0][a]
@@ -228,10 +260,11 @@ __global__ void mmpc_cold_xguess(int B, int NS, int NX, int clip, const MmpcPara
 
 // the signature of mmpc_solve_kernel<> and mmpc_solve_kernel_static<>, and that of mmpc_fast_kernel<>
 typedef void (*mmpc_gen_fn)(const MmpcParams *, int, const double *, const double *, const double *, const double *, const double *,
-                            const double *, double *, double *, double *, int *, int *, double *, double *, const int *, double *, int);
+                            const double *, double *, double *, double *, int *, int *, double *, double *, const int *, double *, int,
+                            const long long *);
 typedef void (*mmpc_fast_fn)(const MmpcParams *, int, const double *, const double *, const double *, const double *, const double *,
                              const double *, double *, double *, double *, int *, int *, double *, double *, const int *, int, double *,
-                             int, const int *, const int *, double *, double *, int);
+                             int, const int *, const int *, double *, double *, int, const long long *);
 
 struct mmpc_handle_s {
     mmpc_config cfg;
@@ -241,6 +274,7 @@ struct mmpc_handle_s {
     // the handle's kernels, resolved once by mmpc_create (resolve_kernels)
     mmpc_gen_fn gen_fn;     // generic: mmpc_solve_kernel<kind>, or the shape's static-LDS instantiation (MMPC_STATIC_LIST)
     int gen_dyn_lds;        // dynamic LDS of a gen_fn launch: lds_bytes, or 0 for a static-LDS instantiation
+    const long long *d_tick;   // obs_per_stage = 2: the registered clock [max_batch] (mmpc_set_obstacle_clock; null: tick 0)
     mmpc_fast_fn fast_fn[2];   // specialised [CONT] for the handle's obs_per_stage; null: (kind, N, M) has none (MMPC_FAST_LIST) or L > 0
     int fast_lds_bytes;
     int per_cu, fast_per_cu;   // resident workgroups (= problems) per CU the runtime reports for the two kernels
@@ -281,6 +315,12 @@ static int fail(mmpc_handle h, int code, const char *fmt, const char *a = "", co
         hipError_t e_ = (call);                                                           \
         if (e_ != hipSuccess) return fail(h, MMPC_E_HIP, "%s: %s", #call, hipGetErrorString(e_)); \
     } while (0)
+
+// doubles of an instance's obstacles, as every solve entry point takes them: static record, table per stage, or motion record
+static size_t obs_doubles(mmpc_handle h) {
+    const size_t M = (size_t)h->cfg.M;
+    return h->hp.obs_per_stage == 2 ? M * 5 : (size_t)(h->hp.obs_per_stage ? h->cfg.N + 1 : 1) * M * 3;
+}
 
 static void default_weights(mmpc_handle h) {
     // mpc_wholebody_qref.py:12-16 / mpc_base.py:11-14
@@ -355,8 +395,10 @@ static void resolve_kernels(mmpc_handle h) {
     const MmpcParams &p = h->hp;
     h->fast_fn[0] = h->fast_fn[1] = nullptr;   // (no list entry for the shape: no specialised kernel, nothing of its sizes)
     h->fast_lds_bytes = h->state_doubles = h->gscr_doubles = 0;
-    const mmpc_gen_fn by_kind[3] = {mmpc_solve_kernel<0>, mmpc_solve_kernel<1>, mmpc_solve_kernel<2>};
-    h->gen_fn = by_kind[c.kind];
+    // (the motion mode has run-time-sized instantiations of its own: the mode is a compile-time constant of every kernel)
+    const mmpc_gen_fn by_kind[2][3] = {{mmpc_solve_kernel<0>, mmpc_solve_kernel<1>, mmpc_solve_kernel<2>},
+                                       {mmpc_solve_kernel<0, 0, -1, 2>, mmpc_solve_kernel<1, 0, -1, 2>, mmpc_solve_kernel<2, 0, -1, 2>}};
+    h->gen_fn = by_kind[p.obs_per_stage == 2][c.kind];
     h->gen_dyn_lds = h->lds_bytes;
     if (!getenv("MMPC_NO_STATIC_GENERIC")) {
 #define MMPC_X(K, NN, MM, OO, LL, AA)                                                                                      \
@@ -369,8 +411,9 @@ static void resolve_kernels(mmpc_handle h) {
     }
 #define MMPC_X(K, NN, MM, WW)                                                                                              \
     if (c.kind == K && c.N == NN && c.M == MM && c.L == 0) {                                                                 \
-        const mmpc_fast_fn by_ops[2][2] = {{mmpc_fast_kernel<K, NN, MM, WW, false, 0>, mmpc_fast_kernel<K, NN, MM, WW, true, 0>},  \
-                                           {mmpc_fast_kernel<K, NN, MM, WW, false, 1>, mmpc_fast_kernel<K, NN, MM, WW, true, 1>}}; \
+        const mmpc_fast_fn by_ops[3][2] = {{mmpc_fast_kernel<K, NN, MM, WW, false, 0>, mmpc_fast_kernel<K, NN, MM, WW, true, 0>},  \
+                                           {mmpc_fast_kernel<K, NN, MM, WW, false, 1>, mmpc_fast_kernel<K, NN, MM, WW, true, 1>},  \
+                                           {mmpc_fast_kernel<K, NN, MM, WW, false, 2>, mmpc_fast_kernel<K, NN, MM, WW, true, 2>}}; \
         h->fast_fn[0] = by_ops[p.obs_per_stage][0];                                                                          \
         h->fast_fn[1] = by_ops[p.obs_per_stage][1];                                                                          \
         h->state_doubles = mmpc_fast_state_doubles<K, NN>(MM);                                                               \
@@ -387,6 +430,7 @@ extern "C" int mmpc_create(const mmpc_config *cfg, mmpc_handle *out) {
     if (cfg->kind != MMPC_KIND_WHOLEBODY && cfg->kind != MMPC_KIND_BASE && cfg->kind != MMPC_KIND_WHOLEBODY_POSE) return MMPC_E_ARG;
     if (cfg->N < 1 || cfg->N > 63 || cfg->M < 0 || cfg->M > 16 || cfg->max_batch < 1) return MMPC_E_ARG;
     if (cfg->L < 0 || cfg->L > 8 || (cfg->L > 0 && cfg->kind != MMPC_KIND_WHOLEBODY)) return MMPC_E_ARG;
+    if (cfg->obs_per_stage < 0 || cfg->obs_per_stage > 2) return MMPC_E_ARG;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || cfg->device < 0 || cfg->device >= ndev) return MMPC_E_NODEVICE;
     mmpc_handle h = new (std::nothrow) mmpc_handle_s();
@@ -399,7 +443,7 @@ extern "C" int mmpc_create(const mmpc_config *cfg, mmpc_handle *out) {
     *out = h;  // returned even on failure below so that the caller can read the error text
     HIPCHK(h, hipSetDevice(cfg->device));
     MmpcParams &p = h->hp;
-    p.N = cfg->N; p.M = cfg->M; p.obs_per_stage = cfg->obs_per_stage ? 1 : 0;
+    p.N = cfg->N; p.M = cfg->M; p.obs_per_stage = cfg->obs_per_stage;
     p.max_iter = cfg->max_iter > 0 ? cfg->max_iter : 2000;   // the reference passes ipopt.max_iter 2000 (mpc_wholebody_qref.py:280)
     p.use_xguess = 0; p.terminal_xy_eq = 0; p.u_guess = nullptr;
     p.dt = cfg->dt; p.tol = cfg->tol > 0 ? cfg->tol : 1e-8; p.mu_init = cfg->mu_init > 0 ? cfg->mu_init : 1.0;
@@ -424,7 +468,7 @@ extern "C" int mmpc_create(const mmpc_config *cfg, mmpc_handle *out) {
     HIPCHK(h, hipOccupancyMaxActiveBlocksPerMultiprocessor(&h->per_cu, h->gen_fn, MMPC_WAVE, h->gen_dyn_lds));
     if (h->fast_fn[0]) HIPCHK(h, hipOccupancyMaxActiveBlocksPerMultiprocessor(&h->fast_per_cu, h->fast_fn[0], MMPC_WAVE, 0));
     const size_t B = (size_t)cfg->max_batch, N = (size_t)cfg->N, nx = (size_t)h->nx, nu = (size_t)h->nu;
-    const size_t nobs = (size_t)(p.obs_per_stage ? N + 1 : 1) * (size_t)cfg->M * 3;
+    const size_t nobs = obs_doubles(h);
     HIPCHK(h, hipMalloc(&h->dp, sizeof(MmpcParams)));
     HIPCHK(h, hipMalloc(&h->d_x_init, B * nx * 8));
     HIPCHK(h, hipMalloc(&h->d_traj, B * (N + 1) * nx * 8));
@@ -546,6 +590,10 @@ static int launch(mmpc_handle h, int B, const MmpcBatch &a, hipStream_t st, cons
     const bool history = lpt && h->hint_on == 1 && h->order_B == B;
     const int key_planes = (h->cfg.kind == MMPC_KIND_WHOLEBODY && h->hp.L > 0) ? h->hp.L : 0;
     if (lpt && !history && (h->cfg.M > 0 || key_planes)) {
+        if (h->hp.obs_per_stage == 2)
+            hipLaunchKernelGGL(mmpc_difficulty_key_motion, dim3((B + 63) / 64), dim3(64), 0, st, B, h->cfg.N, h->cfg.M, h->nref, a.traj,
+                               a.obs, h->d_key, h->dp, a.x_init, key_planes, h->d_tick);
+        else
         hipLaunchKernelGGL(mmpc_difficulty_key, dim3((B + 63) / 64), dim3(64), 0, st, B, h->cfg.N, h->cfg.M, h->nref,
                            h->hp.obs_per_stage, a.traj, a.obs, h->d_key, h->dp, a.x_init, key_planes);
         hipLaunchKernelGGL(mmpc_lpt_order, dim3(1), dim3(MMPC_LPT_THREADS), 0, st, B, h->d_key, h->d_order);
@@ -559,10 +607,10 @@ static int launch(mmpc_handle h, int B, const MmpcBatch &a, hipStream_t st, cons
                            h->dp, B, a.x_init, a.traj, a.uref, a.ulast, a.xguess, a.obs, a.X, a.U, a.s, a.status, a.iters, a.cost, a.err,
                            resume ? h->d_list : order, resume ? 0 : h->budget, cont ? h->d_state : (double *)nullptr,
                            cont ? h->state_doubles : 0, resume ? h->d_count : (const int *)nullptr,
-                           resume ? (const int *)nullptr : ucount, h->d_gscr, h->d_soc, h->soc_doubles);
+                           resume ? (const int *)nullptr : ucount, h->d_gscr, h->d_soc, h->soc_doubles, h->d_tick);
     } else
         hipLaunchKernelGGL(h->gen_fn, dim3(B), dim3(MMPC_WAVE), h->gen_dyn_lds, st, h->dp, B, a.x_init, a.traj, a.uref, a.ulast,
-                           a.xguess, a.obs, a.X, a.U, a.s, a.status, a.iters, a.cost, a.err, order, h->d_soc, h->soc_doubles);
+                           a.xguess, a.obs, a.X, a.U, a.s, a.status, a.iters, a.cost, a.err, order, h->d_soc, h->soc_doubles, h->d_tick);
     HIPCHK(h, hipGetLastError());
     if (use_fast && h->budget > 0 && !resume) {
         // who is suspended: compacted list for mmpc_resume_batch_device
@@ -646,6 +694,17 @@ extern "C" int mmpc_set_warm_start(mmpc_handle h, const double *d_u_guess, doubl
     return upload_params(h);
 }
 
+extern "C" int mmpc_set_obstacle_clock(mmpc_handle h, const long long *d_tick) {
+    if (!h) return MMPC_E_ARG;
+    if (h->hp.obs_per_stage != 2)
+        return fail(h, MMPC_E_UNSUPPORTED, "mmpc_set_obstacle_clock: %s%s", "needs a handle created with obs_per_stage = 2 (motion record)");
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    // (the kernels read the array at launch time: wait for the handle's launches in flight before the pointer they were given goes)
+    if (h->ev_valid) HIPCHK(h, hipEventSynchronize(h->ev));
+    h->d_tick = d_tick;
+    return MMPC_OK;
+}
+
 extern "C" int mmpc_solve_batch_device(mmpc_handle h, int B, const double *d_x_init, const double *d_traj_ref,
                                        const double *d_u_ref, const double *d_u_last, const double *d_x_guess,
                                        const double *d_obs, double *d_X, double *d_U, double *d_s, int *d_status,
@@ -676,7 +735,7 @@ extern "C" int mmpc_solve_batch(mmpc_handle h, int B, const double *x_init, cons
         return fail(h, MMPC_E_ARG, "mmpc_solve_batch: %s%s", "bad argument (B must be in 1..max_batch)");
     HIPCHK(h, hipSetDevice(h->cfg.device));
     const size_t N = (size_t)h->cfg.N, nx = (size_t)h->nx, nu = (size_t)h->nu, b = (size_t)B;
-    const size_t nobs = (size_t)(h->hp.obs_per_stage ? N + 1 : 1) * (size_t)h->cfg.M * 3;
+    const size_t nobs = obs_doubles(h);
     hipStream_t st = 0;
     HIPCHK(h, hipMemcpyAsync(h->d_x_init, x_init, b * nx * 8, hipMemcpyHostToDevice, st));
     HIPCHK(h, hipMemcpyAsync(h->d_traj, traj_ref, b * (N + 1) * (size_t)h->nref * 8, hipMemcpyHostToDevice, st));
@@ -813,7 +872,9 @@ extern "C" int mmpc_tick_prepare_device(mmpc_handle h, int B, double *d_x, long 
                                         void *stream) {
     if (!h) return MMPC_E_ARG;
     if (h->cfg.kind != MMPC_KIND_WHOLEBODY || !h->hp.obs_per_stage)
-        return fail(h, MMPC_E_UNSUPPORTED, "mmpc_tick_prepare_device: %s%s", "needs a whole-body handle (joint-space reference) created with obs_per_stage = 1");
+        return fail(h, MMPC_E_UNSUPPORTED, "mmpc_tick_prepare_device: %s%s", "needs a whole-body handle (joint-space reference) created with obs_per_stage = 1 or 2");
+    if (h->hp.obs_per_stage == 2 && d_obs)
+        return fail(h, MMPC_E_ARG, "mmpc_tick_prepare_device: %s%s", "d_obs must be NULL on a motion handle (obs_per_stage = 2): the kernels form the centres from the record and the clock");
     if (B == 0) return MMPC_OK;
     if (B < 1 || B > h->cfg.max_batch) return fail(h, MMPC_E_ARG, "mmpc_tick_prepare_device: %s%s", "B must be in 0..max_batch");
     if (!d_x) return fail(h, MMPC_E_ARG, "mmpc_tick_prepare_device: %s%s", "d_x is required");

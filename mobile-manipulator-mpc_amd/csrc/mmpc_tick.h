@@ -68,15 +68,8 @@ MMPC_DEV double mmpc_tick_dist(double px, double py, const double *row) {
     return sqrt(dx * dx + dy * dy);
 }
 
-// centre of an obstacle at time t: c + v t
-MMPC_DEV double mmpc_tick_centre(double c, double v, double t) {
-#pragma clang fp contract(off)
-    return c + v * t;
-}
-MMPC_DEV double mmpc_tick_time(long long tick, int k, double dt) {
-#pragma clang fp contract(off)
-    return (double)(tick + k) * dt;
-}
+// (centre of an obstacle at time t and the time of stage k: mmpc_tick_centre, mmpc_tick_time of mmpc_core.h, which the solver
+//  kernels' motion mode shares)
 
 MMPC_DEV void mmpc_tick_one(const MmpcParams &P, const MmpcTickIO io, double *lds MMPC_EMU_ARG) {
     const int N = P.N, M = P.M;

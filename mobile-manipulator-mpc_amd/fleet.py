@@ -22,13 +22,23 @@ plant step, clip, nearest plan point, window, obstacle table) instead of the tor
 sets alternate, so the previous optimum is never copied.  warm_start="shifted" (fused only) starts every solve from tick 1 on at
 the previous optimum shifted one stage and its roll-out, which the same kernel writes, with mu_0 = 0.1 (mmpc_set_warm_start):
 the NLP of every tick is unchanged (U_last stays the previous optimum), the iteration counts are less than half.
+
+obstacles="motion": the handles take the motion record (B, M, 5) = (c_x, c_y, r, v_x, v_y), built once from obs0 and vel, and
+a clock of per-robot tick counts (mmpc_set_obstacle_clock) instead of the (B, N+1, M, 3) table of every tick: the solver kernels
+form the table's centres where they read them, so every number is the table mode's, bit for bit, and no table is allocated,
+written or streamed anywhere.  The clock is the tick tensor the drivers advance anyway (in place; run_async keeps one per buffer
+set, filled next to x_in, so that a continuation on the side stream reads the ticks of its own launch).
 """
 import numpy as np
 
 
 class DeviceFleet:
-    def __init__(self, mm, x0, glob, obs0, vel, N=30, device=0, dt=0.1, handles=3, fused=False, warm_start="reference"):
+    def __init__(self, mm, x0, glob, obs0, vel, N=30, device=0, dt=0.1, handles=3, fused=False, warm_start="reference", obstacles="table"):
         import torch
+        if obstacles not in ("table", "motion"):
+            raise ValueError("obstacles must be 'table' or 'motion', not %r" % (obstacles,))
+        self.obstacles = obstacles
+        self.motion = obstacles == "motion"
         if warm_start not in ("reference", "shifted"):
             raise ValueError("warm_start must be 'reference' or 'shifted', not %r" % (warm_start,))
         if warm_start == "shifted" and not fused:
@@ -38,7 +48,8 @@ class DeviceFleet:
         self.B, self.N, self.M, self.dt = int(x0.shape[0]), int(N), int(obs0.shape[1]), float(dt)
         self.dev = torch.device("cuda", device)
         B, M = self.B, self.M
-        mk = lambda: mm.MPCWholeBody(mm.MobileManipulator(dt), [], [], N=N, max_batch=max(B, 1), device=device, n_obstacles=M, obs_per_stage=True)
+        mk = lambda: mm.MPCWholeBody(mm.MobileManipulator(dt), [], [], N=N, max_batch=max(B, 1), device=device, n_obstacles=M,
+                                     obs_per_stage="motion" if self.motion else True)
         # [0]: lock step (plain kernel); [1], [2]: the two alternating handles of run_async, created on its first call.  A handle owns
         # max_batch rows of device state: staging, warm start, the second-order-correction scratch and - long horizons - the gain
         # blocks (mmpc_create: about 0.5 MB per robot at N = 30, M = 8)
@@ -54,6 +65,11 @@ class DeviceFleet:
         self.uref = torch.zeros((B, N, 5), **f64)
         self.karr = torch.arange(N + 1, **f64)
         self.rows = torch.arange(B, device=self.dev)
+        if self.motion:
+            # the record, once; the lock-step clock: max_batch rows, registered once on the lock-step handle, advanced in place
+            self.rec = torch.cat([self.obs0, self.vel], dim=2).contiguous()
+            self._clock0 = torch.zeros(max(B, 1), dtype=torch.int64, device=self.dev)
+            self.engs[0].set_obstacle_clock(self._clock0)
 
     # ---- per-robot pieces (torch ops on the device)
     def plant(self, x, u):
@@ -67,13 +83,19 @@ class DeviceFleet:
 
     def inputs(self, x, tick, loc_out=None, obs_out=None):
         """local reference window (nearest point of the global plan, tail padded: interface_wholebody_qref.py:377-389) and the
-        per-stage obstacle table of every robot at ITS tick (a (B,) tensor)."""
+        per-stage obstacle table of every robot at ITS tick (a (B,) tensor); obstacles="motion": the record in the table's place
+        (the tick reaches the solve through the handle's clock)."""
         torch = self.torch
         B, N = self.B, self.N
         d = torch.linalg.norm(x[:, None, :2] - self.glob[:, :, :2], dim=2)
         start = torch.argmin(d, dim=1)
         idx = torch.clamp(start[:, None] + torch.arange(N + 1, device=self.dev)[None, :], max=self.nglob - 1)
         loc = torch.gather(self.glob, 1, idx[:, :, None].expand(B, N + 1, 9))
+        if self.motion:
+            if loc_out is not None:
+                loc_out.copy_(loc)
+                return loc_out, self.rec
+            return loc.contiguous(), self.rec
         obs = self.obs0[:, None, :, :].repeat(1, N + 1, 1, 1)
         tk = (tick.to(torch.float64)[:, None] + self.karr[None, :]) * self.dt                   # (B, N+1)
         obs[..., :2] += self.vel[:, None, :, :] * tk[:, :, None, None]
@@ -104,7 +126,7 @@ class DeviceFleet:
         eng.set_iteration_budget(0); eng.reset()
         x = self.x0.clone(); ul = torch.zeros((B, N, 5), **self.f64)
         hist = torch.zeros((B, T, 5), **self.f64); its = torch.zeros((B, T), dtype=torch.int32, device=self.dev)
-        tick = torch.zeros(B, dtype=torch.int64, device=self.dev)
+        tick = self._clock0.zero_()[:B] if self.motion else torch.zeros(B, dtype=torch.int64, device=self.dev)
         out = None
         ok = torch.ones((), dtype=torch.bool, device=self.dev)
         for t in range(T):
@@ -135,14 +157,16 @@ class DeviceFleet:
                                  status=torch.zeros(B, dtype=torch.int32, device=dev), iters=torch.zeros(B, dtype=torch.int32, device=dev),
                                  cost=torch.zeros(B, **self.f64), err=torch.zeros(B, **self.f64))
             self._fsets = [mkout(), mkout()]
-            self._fin = dict(x_in=torch.zeros((B, 9), **self.f64), loc=torch.zeros((B, N + 1, 9), **self.f64), obs=torch.zeros((B, N + 1, M, 3), **self.f64),
-                             zero=torch.zeros((B, N, 5), **self.f64))
+            self._fin = dict(x_in=torch.zeros((B, 9), **self.f64), loc=torch.zeros((B, N + 1, 9), **self.f64),
+                             obs=self.rec if self.motion else torch.zeros((B, N + 1, M, 3), **self.f64), zero=torch.zeros((B, N, 5), **self.f64))
             if shifted:
                 self._fin.update(ug=torch.zeros((B, N, 5), **self.f64), xg=torch.zeros((B, N + 1, 9), **self.f64))
         F = self._fin
         eng.set_iteration_budget(0); eng.reset()
         x = self.x0.clone()
-        tick = torch.zeros(B, dtype=torch.int64, device=dev)
+        tick = self._clock0.zero_()[:B] if self.motion else torch.zeros(B, dtype=torch.int64, device=dev)
+        # (motion: no table - the tick kernel only advances the clock the solve reads)
+        tab = dict() if self.motion else dict(obs0=self.obs0, vel=self.vel, obs=F["obs"])
         hist = torch.zeros((B, T, 5), **self.f64); its = torch.zeros((B, T), dtype=torch.int32, device=dev)
         sts = torch.zeros((B, T), dtype=torch.int32, device=dev)
         ug, xg = (F["ug"], F["xg"]) if shifted else (None, None)
@@ -151,8 +175,8 @@ class DeviceFleet:
             for t in range(T):
                 out = self._fsets[t & 1]
                 warm = shifted and prev is not None
-                eng.tick_prepare(x, tick, U_prev=prev, glob=self.glob, obs0=self.obs0, vel=self.vel, x_in=F["x_in"], traj_ref=F["loc"], obs=F["obs"],
-                                 u_guess=ug if warm else None, x_guess=xg if warm else None)
+                eng.tick_prepare(x, tick, U_prev=prev, glob=self.glob, x_in=F["x_in"], traj_ref=F["loc"],
+                                 u_guess=ug if warm else None, x_guess=xg if warm else None, **tab)
                 if warm and t == 1:
                     eng.set_warm_start(ug, 0.1)          # (waits for tick 0's solve: the one host synchronisation of a run)
                 eng.solve_batch_device(F["x_in"], F["loc"], self.uref, prev if prev is not None else F["zero"], F["obs"],
@@ -193,7 +217,7 @@ class DeviceFleet:
             for g in range(G):
                 lo, hi = sharding.shard_bounds(self.B, G, g)
                 sub = DeviceFleet(mm, self.x0[lo:hi], self.glob[lo:hi], self.obs0[lo:hi], self.vel[lo:hi], N=self.N, device=self.dev.index, dt=self.dt,
-                                  handles=1, fused=self.fused, warm_start=self.warm_start)
+                                  handles=1, fused=self.fused, warm_start=self.warm_start, obstacles=self.obstacles)
                 # (priority: lower number = served first; the last group runs at the default priority)
                 pr = (max(hi_pr, min(lo_pr, 0 - (G - 1 - g))) if hi_pr < 0 else 0) if priority else 0
                 self._groups.append((lo, hi, sub, torch.cuda.Stream(device=self.dev, priority=pr)))
@@ -244,9 +268,15 @@ class DeviceFleet:
                          status=torch.zeros(B, dtype=torch.int32, device=dev), iters=torch.zeros(B, dtype=torch.int32, device=dev),
                          cost=torch.zeros(B, **self.f64), err=torch.zeros(B, **self.f64))
                 self._sets.append(dict(out=o, x_in=torch.zeros((B, 9), **self.f64), loc=torch.zeros((B, N + 1, 9), **self.f64),
-                                       obs=torch.zeros((B, N + 1, M, 3), **self.f64), ul_in=torch.zeros((B, N, 5), **self.f64),
+                                       obs=self.rec if self.motion else torch.zeros((B, N + 1, M, 3), **self.f64),
+                                       ul_in=torch.zeros((B, N, 5), **self.f64),
                                        list=torch.zeros(B, dtype=torch.int32, device=dev), count=torch.zeros(1, dtype=torch.int32, device=dev),
                                        susp=torch.zeros(B, dtype=torch.bool, device=dev), ev=None))
+                if self.motion:
+                    # the clock of this buffer set, registered once on the set's handle: a launch and its continuation read these
+                    # ticks, whatever the robots of the other set do meanwhile
+                    self._sets[s]["tick"] = torch.zeros(max(B, 1), dtype=torch.int64, device=dev)
+                    self.engs[1 + s].set_obstacle_clock(self._sets[s]["tick"])
         for s in range(2):
             self.engs[1 + s].set_iteration_budget(budget); self.engs[1 + s].reset()
             self._sets[s]["ev"] = None; self._sets[s]["susp"].zero_()
@@ -285,6 +315,8 @@ class DeviceFleet:
                 inflight = inflight & ~m
             ready = (~inflight) & (state["tick"] < T)
             S["x_in"].copy_(state["x"]); S["ul_in"].copy_(state["ul"])
+            if self.motion:
+                S["tick"][:B].copy_(state["tick"])
             self.inputs(state["x"], state["tick"], S["loc"], S["obs"])
             score = torch.where(ready, state["prev_it"] + 1.0, torch.zeros_like(state["prev_it"]))
             S["list"].copy_(torch.argsort(score, descending=True, stable=True).to(torch.int32))
