@@ -178,6 +178,23 @@ int mmpc_set_warm_start(mmpc_handle h, const double *d_u_guess, double mu_init);
  * obstacle is now and how fast it moves") fills the record per solve and leaves the clock at NULL. */
 int mmpc_set_obstacle_clock(mmpc_handle h, const long long *d_tick);
 
+/* Objective scaling, opt-in: IPOPT's nlp_scaling_method = gradient-based with nlp_scaling_max_gradient = max_gradient (and
+ * nlp_scaling_min_value = 1e-8) - the defaults the reference's solver runs under, since its option dict names neither
+ * (controllers/mpc_wholebody_qref.py:280-285).  Per instance: g = max-norm of the objective's gradient over all of (X, U, s) at the
+ * starting point the solve is given (X = tile(clip(x_init)) or the X guess, U = u_last or the opt-in U guess, s = 0; before the
+ * bound push), sigma = g > max_gradient ? max(max_gradient / g, 1e-8) : 1, and the solve is the solve of the NLP with objective
+ * sigma f: tolerance, termination test, barrier schedule and filter all act on the scaled problem, as in IPOPT.  out_cost stays the
+ * unscaled objective f(X, U, s); out_err is the scaled problem's error.  IPOPT's scaling of constraint rows (rows whose gradient
+ * exceeds the same bound) is not modelled because it cannot fire: every row of this NLP has a gradient of max-norm at most about 1
+ * (circle rows: unit vectors; dynamics rows: 1 and dt; self-collision rows: arm lengths below 1 m), far from any sensible bound.
+ * max_gradient = 0 (the default) is off: a solve is then bit for bit the solve without this call.  IPOPT's value is 100.  A negative
+ * or non-finite max_gradient is MMPC_E_ARG.  d_scale_out [max_batch] (device memory, may be NULL) stays registered until the next
+ * call and receives sigma_b of every instance a launch solves, indexed by instance ROW (list launches and continuations included; a
+ * continuation goes on with the factor of the solve it continues).  Applies to every solve entry point and both kernel families; the
+ * LDS per problem and the problems per CU do not change.  Keep the setting unchanged between a budgeted launch and its continuations.
+ * The call waits for the handle's launches in flight. */
+int mmpc_set_objective_scaling(mmpc_handle h, double max_gradient, double *d_scale_out);
+
 /* Launch order of the workgroups (= instances) of a batch.  A batch takes as long as its last wave, so the instances
  * that need the most interior-point iterations should start first.  mode 1 (default): longest-first by the iteration counts
  * of the handle's previous launch of the same B when there is one (a receding-horizon loop solves the same robots every
@@ -237,7 +254,7 @@ int mmpc_tick_prepare_device(mmpc_handle h, int B, double *d_x, long long *d_tic
  * warm start).  Calls on one handle must come from one host thread at a time.  Launches may use different streams:
  * a launch on another stream than the handle's previous one is ordered after it (event wait), and the entry points
  * that change the parameter block or the warm start (mmpc_set_weights, mmpc_set_terminal_xy_equality,
- * mmpc_set_warm_start, mmpc_set_obstacle_clock, mmpc_reset, mmpc_get/set_u_latest) wait for the handle's launches in flight first. */
+ * mmpc_set_warm_start, mmpc_set_obstacle_clock, mmpc_set_objective_scaling, mmpc_reset, mmpc_get/set_u_latest) wait for the handle's launches in flight first. */
 
 /* bytes of LDS one problem instance occupies (one 64-lane workgroup) */
 int mmpc_lds_bytes(mmpc_handle h);

@@ -24,7 +24,7 @@ class MmpcConfig(C.Structure):
 EXPORTS = ["mmpc_create", "mmpc_destroy", "mmpc_set_weights", "mmpc_set_terminal_xy_equality", "mmpc_reset",
            "mmpc_solve_batch", "mmpc_solve_batch_device", "mmpc_get_u_latest", "mmpc_set_u_latest",
            "mmpc_lds_bytes", "mmpc_problems_per_cu", "mmpc_set_warm_start", "mmpc_set_schedule_hint", "mmpc_set_iteration_budget", "mmpc_resume_batch_device", "mmpc_solve_list_device", "mmpc_suspended_count", "mmpc_last_error", "mmpc_version", "mmpc_ik_batch", "mmpc_ik_batch_device",
-           "mmpc_tick_prepare_device", "mmpc_set_obstacle_clock"]
+           "mmpc_tick_prepare_device", "mmpc_set_obstacle_clock", "mmpc_set_objective_scaling"]
 
 _lib = None
 _dp = C.POINTER(C.c_double)
@@ -71,6 +71,7 @@ def lib():
         L.mmpc_ik_batch_device.argtypes = [C.c_int, C.c_int] + [C.c_void_p] * 5 + [C.c_void_p]
         L.mmpc_tick_prepare_device.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 8 + [C.c_void_p]
         L.mmpc_set_obstacle_clock.argtypes = [C.c_void_p, C.c_void_p]
+        L.mmpc_set_objective_scaling.argtypes = [C.c_void_p, C.c_double, C.c_void_p]
         _lib = L
     return _lib
 
@@ -199,6 +200,31 @@ class Engine:
         self._chk(lib().mmpc_set_obstacle_clock(self._h, C.c_void_p(tick.data_ptr()) if tick is not None else None),
                   "mmpc_set_obstacle_clock")
         self._tick = tick
+
+    def set_objective_scaling(self, max_gradient=100.0, scale_out=None):
+        """mmpc_set_objective_scaling: IPOPT's gradient-based objective scaling (nlp_scaling_max_gradient = max_gradient; 0 switches
+        it off again).  `scale_out`: (max_batch,) cuda float64 tensor that receives the factor of every instance a launch solves
+        (kept alive by the engine) or None."""
+        if scale_out is not None:
+            import torch
+            if (not scale_out.is_cuda or scale_out.dtype != torch.float64 or not scale_out.is_contiguous()
+                    or scale_out.device.index != self.device or tuple(scale_out.shape) != (self.max_batch,)):
+                raise ValueError("scale_out must be a contiguous cuda:%d float64 tensor (max_batch,) = (%d,)" % (self.device, self.max_batch))
+        self._chk(lib().mmpc_set_objective_scaling(self._h, float(max_gradient),
+                                                   C.c_void_p(scale_out.data_ptr()) if scale_out is not None else None),
+                  "mmpc_set_objective_scaling")
+        self._scale_out = scale_out
+
+    def set_nlp_scaling(self, nlp_scaling=None, nlp_scaling_max_gradient=100.0):
+        """The IPOPT options of the same names, as the controllers take them: None / "none" (off: the engine's default) or
+        "gradient-based" (IPOPT's default, which the reference runs under) with its bound on the objective gradient."""
+        if nlp_scaling in (None, "none"):
+            return self.set_objective_scaling(0.0)
+        if nlp_scaling != "gradient-based":
+            raise ValueError("nlp_scaling must be None, 'none' or 'gradient-based' (got %r)" % (nlp_scaling,))
+        if not float(nlp_scaling_max_gradient) > 0:
+            raise ValueError("nlp_scaling_max_gradient must be positive")
+        self.set_objective_scaling(float(nlp_scaling_max_gradient))
 
     def set_schedule_hint(self, mode):
         """mmpc_set_schedule_hint: launch order of a batch's workgroups - 0/False batch order, 1/True (default) longest-first

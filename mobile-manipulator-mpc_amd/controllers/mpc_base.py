@@ -13,7 +13,8 @@ class MPCBase:
                  M=np.diag([1e5]),
                  ulim=np.array([[-2, -PI], [2, PI]]),
                  xlim=np.array([[-100, -100, -2, -2, -PI], [100, 100, 2, 2, PI]]),
-                 max_batch=1, device=0, obs_per_stage=False, n_obstacles=None, tol=1e-8, max_iter=2000):
+                 max_batch=1, device=0, obs_per_stage=False, n_obstacles=None, tol=1e-8, max_iter=2000,
+                 nlp_scaling=None, nlp_scaling_max_gradient=100.0):
         self.Q_value, self.R_value, self.P_value, self.M_value = Q, R, P, M
         self.dt = robot.dt
         self.N = N
@@ -28,6 +29,10 @@ class MPCBase:
         self._engine = _capi.Engine(_capi.KIND_BASE, N, self._M, self.dt, self.ulim, xl,
                                     np.array([[-INF, -INF], [INF, INF]]), max_batch=max_batch, device=device,
                                     obs_per_stage=obs_per_stage, tol=tol, max_iter=max_iter)
+        # nlp_scaling / nlp_scaling_max_gradient: the IPOPT options of these names (the reference leaves them at IPOPT's defaults,
+        # "gradient-based" and 100); None leaves the engine as it is created, without scaling (Engine.set_nlp_scaling)
+        if nlp_scaling is not None:
+            self._engine.set_nlp_scaling(nlp_scaling, nlp_scaling_max_gradient)
         self.max_batch = max_batch
         self.reset()
 

@@ -23,7 +23,8 @@ class MPCWholeBody:
                  xlim=np.array([[-100, -100, -INF, -2, -2, -PI, -PI / 2, -PI * 3 / 4, 0],
                                 [100, 100, INF, 2, 2, PI, PI / 2, 0, PI]]),
                  dulim=np.array([[-INF, -INF, -0.5, -0.5, -0.5], [INF, INF, 0.5, 0.5, 0.5]]),
-                 max_batch=1, device=0, n_obstacles=None, tol=1e-8, max_iter=2000):
+                 max_batch=1, device=0, n_obstacles=None, tol=1e-8, max_iter=2000,
+                 nlp_scaling=None, nlp_scaling_max_gradient=100.0):
         self.N = N
         self.Q, self.R, self.P, self.S, self.W = Q, R, P, S, W
         self.dt = robot.dt
@@ -37,6 +38,10 @@ class MPCWholeBody:
         self._M = len(obstacle_list) if n_obstacles is None else int(n_obstacles)
         self._engine = _capi.Engine(_capi.KIND_WHOLEBODY_POSE, N, self._M, self.dt, self.ulim, self.xlim, self.dulim,
                                     max_batch=max_batch, device=device, tol=tol, max_iter=max_iter)
+        # nlp_scaling / nlp_scaling_max_gradient: the IPOPT options of these names (the reference leaves them at IPOPT's defaults,
+        # "gradient-based" and 100); None leaves the engine as it is created, without scaling (Engine.set_nlp_scaling)
+        if nlp_scaling is not None:
+            self._engine.set_nlp_scaling(nlp_scaling, nlp_scaling_max_gradient)
         self.max_batch = max_batch
         self.reset()
 

@@ -28,7 +28,7 @@ class MPCWholeBody:
                                 [100, 100, INF, 2, 2, PI, PI / 2, 0, 3 * PI / 2]]),
                  dulim=np.array([[-INF, -INF, -0.5, -0.5, -0.5], [INF, INF, 0.5, 0.5, 0.5]]),
                  max_batch=1, device=0, obs_per_stage=False, n_obstacles=None, tol=1e-8, max_iter=2000,
-                 faithful_convex=None):
+                 faithful_convex=None, nlp_scaling=None, nlp_scaling_max_gradient=100.0):
         self.N = N
         self.Q_value, self.R_value, self.P_value, self.S_value, self.W_value = Q, R, P, S, W
         self.dt = robot.dt
@@ -57,6 +57,10 @@ class MPCWholeBody:
         self._engine = _capi.Engine(_capi.KIND_WHOLEBODY, N, self._M, self.dt, self.ulim, self.xlim, self.dulim,
                                     max_batch=max_batch, device=device, obs_per_stage=obs_per_stage, tol=tol,
                                     max_iter=max_iter, halfspaces=hs, as_written=self._q8_check)
+        # nlp_scaling / nlp_scaling_max_gradient: the IPOPT options of these names (the reference leaves them at IPOPT's defaults,
+        # "gradient-based" and 100); None leaves the engine as it is created, without scaling (Engine.set_nlp_scaling)
+        if nlp_scaling is not None:
+            self._engine.set_nlp_scaling(nlp_scaling, nlp_scaling_max_gradient)
         self.max_batch = max_batch
         self.X, self.X_ref = Sym("X"), Sym("X_ref")
         self.reset()

@@ -271,6 +271,10 @@ struct MmpcIO {
     double *gscr;      // this instance's gain block in global memory (specialised kernels of long horizons, MmpcGainBlock), else unused
     double *soc;       // this instance's scratch of the second-order correction in global memory (mmpc_soc_doubles; null: no corrections)
     const long long *tick;   // obs_per_stage = 2: this instance's tick count (null: 0), mmpc_set_obstacle_clock
+    // objective scaling (mmpc_set_objective_scaling): the largest objective-gradient entry the solve accepts at its starting point
+    // (0: off - the kernels then run none of the scaling code), and where this instance's factor goes (null: not wanted)
+    double scale_max_grad;
+    double *scale_out;
 };
 // doubles of an instance's second-order-correction scratch (both kernels; NR = rows per stage that are not box rows): the
 // uncorrected direction, and for the specialised kernels - which move to a trial point in place - the constraint residuals of the
@@ -278,7 +282,8 @@ struct MmpcIO {
 MMPC_HD constexpr int mmpc_soc_doubles(int N, int NX, int NU, int NR) { return (N + 1) * (4 * NX + NU + 1 + 2 * NR) + 8; }
 // Instance b of a batch: the one place where the batch's pointers become an instance's slices (every solve kernel and both
 // runners of the host emulation).  so = doubles of an instance's obstacle table; soc_stride = doubles of its correction scratch.
-// The budget fields are the specialised kernels' own, the tick is the motion mode's: the kernel wrappers set them after the call.  (Filled in place: returned by value the
+// The budget fields are the specialised kernels' own, the tick is the motion mode's, the two scaling fields the objective scaling's:
+// the kernel wrappers set them after the call.  (Filled in place: returned by value the
 // struct travels through a noalias return slot, whose scopes on every access here change the kernels' code.)
 template <int KIND>
 MMPC_DEV void mmpc_instance_io(MmpcIO &io, const MmpcParams &P, int b, int N, size_t so, const double *x_init,
@@ -301,6 +306,7 @@ MMPC_DEV void mmpc_instance_io(MmpcIO &io, const MmpcParams &P, int b, int N, si
     io.cost = cost + b;
     io.err = err + b;
     io.state = nullptr; io.budget = 0; io.resume = 0; io.gscr = nullptr; io.tick = nullptr;
+    io.scale_max_grad = 0.0; io.scale_out = nullptr;
     io.soc = soc ? soc + (size_t)b * soc_stride : nullptr;
 }
 
@@ -336,6 +342,14 @@ MMPC_DEV MmpcObs mmpc_obs_motion(const double *rec, int M, int k, int m, double 
 }
 
 MMPC_DEV double mmpc_min(double a, double b) { return a < b ? a : b; }
+// ---- objective scaling (opt-in; IPOPT's nlp_scaling_method = gradient-based, IpGradientScaling): the factor of the objective from
+// g = the max-norm of its gradient at the starting point and G = nlp_scaling_max_gradient; 1e-8 is IPOPT's nlp_scaling_min_value.
+// (A NaN g fails the comparison: factor 1 - the solve reports the NaN itself, status 2.)
+MMPC_DEV double mmpc_scale_factor(double g, double G) {
+    if (!(g > G)) return 1.0;
+    const double f = G / g;
+    return f > 1e-8 ? f : 1e-8;
+}
 MMPC_DEV double mmpc_bound_push(double v, double lo, double hi) {
     double lo2 = lo + MMPC_BOUND_PUSH, hi2 = hi - MMPC_BOUND_PUSH;
     if (lo2 > hi2) lo2 = hi2 = 0.5 * (lo + hi);
@@ -680,7 +694,8 @@ MMPC_DEV void mmpc_solve_one(const MmpcParams &P, const MmpcIO io, double *lds M
            *const QQX = lds + L.QQX, *const HUXS = lds + L.HUXS, *const HUUS = lds + L.HUUS, *const RDX = lds + L.RDX;
     const bool teq = P.terminal_xy_eq != 0;
     const int SL_UHI = NU, SL_XLO = 2 * NU, SL_XHI = 2 * NU + NX, SL_C = 2 * NU + 2 * NX, SL_S = SL_C + M, SL_H = SL_S + NSELF, SL_Q = SL_H + NHS;
-    const double dt = P.dt, Sw = P.S, tol = P.tol;
+    const double dt = P.dt, tol = P.tol;
+    double Sw = P.S, sigma = 1.0;   // (objective scaling: the slack weight becomes P.S sigma; off: sigma is the constant 1 and nothing is multiplied)
 
     // bound of a box slot r at stage k; returns false when the row does not exist
     auto box_bound = [&](int k, int r, double &b) -> bool {
@@ -757,6 +772,35 @@ MMPC_DEV void mmpc_solve_one(const MmpcParams &P, const MmpcIO io, double *lds M
     } else
     for (int i = lane; i < (OPS ? NS : 1) * M * 3; i += MMPC_WAVE) OBS[i] = io.obs[i];
     LANES_END
+    // ---------------------------------------------------------------- objective scaling (opt-in, a uniform branch): the solve is the
+    // solve of sigma f, sigma from the gradient of f at the starting point as it stands here - before the bound push, s = 0 (so
+    // the slack term adds nothing).  The weights' copies in WTS and the slack weight are multiplied once; nothing else changes.
+    if (io.scale_max_grad > 0.0) {
+        LANES_BEGIN
+        double gm = 0.0;
+        for (int k = lane; k < NS; k += MMPC_WAVE) {
+            double g[NX];
+            mmpc_state_cost<KIND>(WTS, k == N, X + k * NX, XREF + k * NREF, g, nullptr, false);
+            for (int i = 0; i < NX; i++) gm = mmpc_max(gm, fabs(g[i]));
+            if (k < N) {
+                const double *uk = U + k * NU;
+                for (int a = 0; a < NU; a++) {
+                    double v = 0.0;
+                    for (int b = 0; b < NU; b++)
+                        v += WTS[MMPC_W_R2 + a * NU + b] * (uk[b] - UREF[k * NU + b]) + WTS[MMPC_W_W2 + a * NU + b] * (uk[b] - ULAST[k * NU + b]);
+                    gm = mmpc_max(gm, fabs(v));
+                }
+            }
+        }
+        RED[lane] = gm;
+        LANES_END
+        sigma = MMPC_UNIFORM(mmpc_scale_factor(MMPC_GRED_MAX(RED), io.scale_max_grad));
+        LANES_BEGIN
+        for (int i = lane; i < MMPC_W_XLIM; i += MMPC_WAVE) WTS[i] *= sigma;
+        if (lane == 0 && io.scale_out) *io.scale_out = sigma;
+        LANES_END
+        Sw = MMPC_UNIFORM(P.S * sigma);
+    }
     // bound push of the initial point (needs U_last of the previous phase for the merged input box)
     LANES_BEGIN
     for (int i = lane; i < N * NU; i += MMPC_WAVE) {
@@ -2140,6 +2184,7 @@ MMPC_DEV void mmpc_solve_one(const MmpcParams &P, const MmpcIO io, double *lds M
     LANES_END
     double cost = 0.0;
     cost = MMPC_GRED_SUM(RED);
+    if (io.scale_max_grad > 0.0) cost /= sigma;   // (the reported cost is the objective as the caller wrote it)
     LANES_BEGIN
     if (lane == 0) { *io.status = status; *io.iters = it; *io.cost = cost; *io.err = E0; }
     LANES_END

@@ -187,6 +187,7 @@ struct MmpcFastLayout {
 #define MMPC_C_WR 56       // diag(R2)[5]
 #define MMPC_C_WW 61       // diag(W2)[5]
 #define MMPC_C_RW2 66      // RW2 [25] (full)
+#define MMPC_C_SCALE 91    // factor of the objective (objective scaling; 0 while the option is off: nothing reads it then)
 #define MMPC_C_SIZE 92
 
 // Long horizons (N >= MMPC_SLIM_NMIN) leave the read-only inputs that are touched once or twice per iteration - the
@@ -238,6 +239,7 @@ MMPC_HD constexpr MmpcFastLayout mmpc_fast_layout(int M, int obs_per_stage) {
 
 // doubles of the per-instance save area of a suspended solve: trajectory, slacks, equality multipliers, filter, scalars,
 // and per lane the multipliers of its box rows and the slack / multiplier of its circle and self-collision rows
+// (scalars: 0..9 the loop's own, see the park / resume code; 10 the factor of the objective, CST[MMPC_C_SCALE]; 11 spare)
 #define MMPC_NSCAL 12
 template <int KIND, int N>
 MMPC_HD int mmpc_fast_state_doubles(int MC) {
@@ -418,7 +420,8 @@ MMPC_DEV void mmpc_solve_fast(const MmpcParams &P, const MmpcIO io, double *lds 
         if constexpr (GK) return *(double *)((char *)base + (size_t)((unsigned)idx * 8u)); else return base[idx];
     };
     double *const RB = lds + L.RB, *const RDS = lds + L.RDS, *const Q1V = lds + L.Q1V;   // residual base r[k][v] and the s_k residual of the current point
-    const double dt = P.dt, Sw = P.S, tol = P.tol;
+    const double dt = P.dt, tol = P.tol;
+    double Sw = P.S;   // (objective scaling: P.S times the factor of the objective)
 #ifdef MMPC_EMU
     static thread_local MmpcLaneState<KIND, N, MC> ls_all[MMPC_WAVE];
     static thread_local double wr_all[MMPC_WAVE][9];
@@ -622,6 +625,42 @@ MMPC_DEV void mmpc_solve_fast(const MmpcParams &P, const MmpcIO io, double *lds 
     };
 
     double mu = P.mu_init;
+    // save area of a suspended solve (layout: mmpc_fast_state_doubles)
+    constexpr int MCS = MC > 0 ? MC : 1, NLREG = 2 * NPASS + 2 * MCS + 8;
+    // (offsets into io.state; the pointers are formed where they are used so that nothing of this stays live in the loop)
+    constexpr int ST_S = NPAIR, ST_LAM = NPAIR + NS, ST_FILT = NPAIR + NS + NS * NX, ST_SCAL = ST_FILT + 2 * MMPC_FCAP,
+                  ST_LANE = ST_SCAL + MMPC_NSCAL;
+    // ------------------------------------------------------------------ objective scaling (opt-in, a uniform branch): the solve is
+    // the solve of sigma f, sigma from the max-norm of the gradient of f at the starting point as it stands here - before the bound
+    // push, s = 0 (the slack term adds nothing).  The weights' copies in CST and the slack weight are multiplied once, no read of
+    // them changes; sigma stays in CST[MMPC_C_SCALE] for the reported cost and travels in the save area of a suspended solve, so a
+    // continuation goes on with the factor of ITS solve (its start is no longer the point the factor came from).
+    if (io.scale_max_grad > 0.0) {
+        double sigma;
+        if (CONT && io.resume) sigma = io.state[ST_SCAL + 10];
+        else {
+            LANES_BEGIN
+            double gm = 0.0;
+            for (int idx = lane; idx < NPAIR; idx += MMPC_WAVE) {
+                const int k = idx / NV, v = idx % NV;
+                const double val = XU[idx];
+                double e = val - ref_at(idx, k, v);
+                if (KIND == 1 && v == 2) e = mmpc_angle_diff(val, ref_at(idx, k, v));
+                double g = w_diag(k, v) * e;
+                if (v >= NX && k < N) g += CST[MMPC_C_WW + v - NX] * (val - ulast_at(k, v - NX));
+                gm = mmpc_vmax(gm, fabs(g));
+            }
+            MMPC_WR(0) = gm;
+            LANES_END
+            sigma = mmpc_scale_factor(MMPC_RED_MAX(0), io.scale_max_grad);
+        }
+        sigma = MMPC_UNIFORM(sigma);
+        LANES_BEGIN
+        for (int i = lane + MMPC_C_WQ; i < MMPC_C_SCALE; i += MMPC_WAVE) CST[i] *= sigma;
+        if (lane == 0) { CST[MMPC_C_SCALE] = sigma; if (io.scale_out) *io.scale_out = sigma; }
+        LANES_END
+        Sw = MMPC_UNIFORM(P.S * sigma);
+    }
     // ------------------------------------------------------------------ bound push of the initial point (own phase: the
     //                                                                    stage lanes below read what the pair lanes move)
     LANES_BEGIN
@@ -695,11 +734,6 @@ MMPC_DEV void mmpc_solve_fast(const MmpcParams &P, const MmpcIO io, double *lds 
 
     int status = 1, it = 0, nfilt = 0, filt_init = 0;
     double E0 = 0.0, th_max = 0.0, th_min = 0.0;
-    // save area of a suspended solve (layout: mmpc_fast_state_doubles)
-    constexpr int MCS = MC > 0 ? MC : 1, NLREG = 2 * NPASS + 2 * MCS + 8;
-    // (offsets into io.state; the pointers are formed where they are used so that nothing of this stays live in the loop)
-    constexpr int ST_S = NPAIR, ST_LAM = NPAIR + NS, ST_FILT = NPAIR + NS + NS * NX, ST_SCAL = ST_FILT + 2 * MMPC_FCAP,
-                  ST_LANE = ST_SCAL + MMPC_NSCAL;
     int nsmall_r = 0;
     double prox_r = 0.0, delta_r = 0.0, dprev_r = 0.0;
     if (CONT && io.resume) {
@@ -953,7 +987,8 @@ MMPC_DEV void mmpc_solve_fast(const MmpcParams &P, const MmpcIO io, double *lds 
     for (int i = lane; i < NS; i += MMPC_WAVE) { io.s[i] = S[i]; f += Sw * S[i] * S[i]; }
     MMPC_WR(0) = f;
     LANES_END
-    const double cost = MMPC_RED_SUM(0);
+    double cost = MMPC_RED_SUM(0);
+    if (io.scale_max_grad > 0.0) cost /= CST[MMPC_C_SCALE];   // (the reported cost is the objective as the caller wrote it)
     LANES_BEGIN
     if (lane == 0) { *io.status = status; *io.iters = it; *io.cost = cost; *io.err = E0; }
     LANES_END

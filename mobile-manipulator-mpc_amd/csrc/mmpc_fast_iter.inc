@@ -333,6 +333,7 @@
             if (lane == 0) {
                 st_scal[0] = mu; st_scal[1] = th_max; st_scal[2] = th_min; st_scal[3] = prox;
                 st_scal[4] = (double)it; st_scal[5] = (double)nfilt; st_scal[6] = (double)filt_init; st_scal[7] = (double)nsmall; st_scal[8] = delta_last; st_scal[9] = delta_prev;
+                st_scal[10] = CST[MMPC_C_SCALE];   // (objective scaling: the factor of this solve, read back by its continuation)
             }
             LANES_END
             status = 3;   // MMPC_STATUS_SUSPENDED

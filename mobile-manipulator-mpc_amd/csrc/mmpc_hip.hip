@@ -22,7 +22,8 @@ __global__ __launch_bounds__(MMPC_WAVE) void mmpc_solve_kernel(
     const double *__restrict__ u_ref, const double *__restrict__ u_last, const double *__restrict__ x_guess,
     const double *__restrict__ obs, double *__restrict__ X, double *__restrict__ U, double *__restrict__ s,
     int *__restrict__ status, int *__restrict__ iters, double *__restrict__ cost, double *__restrict__ err,
-    const int *__restrict__ order, double *__restrict__ soc, int soc_stride, const long long *__restrict__ tick) {
+    const int *__restrict__ order, double *__restrict__ soc, int soc_stride, const long long *__restrict__ tick,
+    double scale_max_grad, double *__restrict__ scale_out) {
     extern __shared__ double lds[];
     if ((int)blockIdx.x >= B) return;
     // longest-first schedule hint: workgroup i solves instance order[i] (a permutation; results do not depend on it)
@@ -35,6 +36,7 @@ __global__ __launch_bounds__(MMPC_WAVE) void mmpc_solve_kernel(
     mmpc_instance_io<KIND>(io, P, b, N, so, x_init, traj_ref, u_ref, u_last, x_guess, obs, X, U, s, status, iters, cost, err,
                            soc, soc_stride);
     if (OPSC == 2 && tick) io.tick = tick + b;
+    io.scale_max_grad = scale_max_grad; if (scale_out) io.scale_out = scale_out + b;   // (objective scaling, mmpc_set_objective_scaling; 0: off)
     mmpc_solve_one<KIND, NC, MC, OPSC, LC>(P, io, lds);
 }
 
@@ -47,7 +49,8 @@ __global__ __launch_bounds__(MMPC_WAVE) void mmpc_solve_kernel_static(
     const double *__restrict__ u_ref, const double *__restrict__ u_last, const double *__restrict__ x_guess,
     const double *__restrict__ obs, double *__restrict__ X, double *__restrict__ U, double *__restrict__ s,
     int *__restrict__ status, int *__restrict__ iters, double *__restrict__ cost, double *__restrict__ err,
-    const int *__restrict__ order, double *__restrict__ soc, int soc_stride, const long long *__restrict__ tick) {
+    const int *__restrict__ order, double *__restrict__ soc, int soc_stride, const long long *__restrict__ tick,
+    double scale_max_grad, double *__restrict__ scale_out) {
     constexpr int NHS = (KIND == 0 && LC > 0) ? 6 : 0, NQ = (KIND == 0 && AWC && LC >= 2) ? 6 * (LC - 1) : 0;
     __shared__ double lds[mmpc_layout<KIND>(NC, MC, OPSC, NHS, NQ).total];
     if ((int)blockIdx.x >= B) return;
@@ -59,6 +62,7 @@ __global__ __launch_bounds__(MMPC_WAVE) void mmpc_solve_kernel_static(
     mmpc_instance_io<KIND>(io, P, b, N, so, x_init, traj_ref, u_ref, u_last, x_guess, obs, X, U, s, status, iters, cost, err,
                            soc, soc_stride);
     if (OPSC == 2 && tick) io.tick = tick + b;
+    io.scale_max_grad = scale_max_grad; if (scale_out) io.scale_out = scale_out + b;   // (objective scaling, mmpc_set_objective_scaling; 0: off)
     mmpc_solve_one<KIND, NC, MC, OPSC, LC, AWC>(P, io, lds);
 }
 // (kind, N, M, obs_per_stage, L, as_written): demo_wholebody_qref.py scenario 2 (two planes) as written and with the intended
@@ -80,7 +84,7 @@ __global__ __launch_bounds__(MMPC_WAVE, WPE) void mmpc_fast_kernel(
     int *__restrict__ status, int *__restrict__ iters, double *__restrict__ cost, double *__restrict__ err,
     const int *__restrict__ order, int budget, double *__restrict__ state, int state_stride, const int *__restrict__ resume_count,
     const int *__restrict__ list_count, double *__restrict__ gscr, double *__restrict__ soc, int soc_stride,
-    const long long *__restrict__ tick) {
+    const long long *__restrict__ tick, double scale_max_grad, double *__restrict__ scale_out) {
     __shared__ double lds[mmpc_fast_layout<KIND, N>(MC, OPS).total];
     // A continuation launch (resume_count != null): `order` is the compacted list of the suspended instances, *resume_count its
     // length, and the grid is SMALL (MMPC_RESUME_GRID workgroups that stride over the list): a handful of instances is left,
@@ -106,6 +110,7 @@ __global__ __launch_bounds__(MMPC_WAVE, WPE) void mmpc_fast_kernel(
         io.resume = resume_count ? 1 : 0;
         io.gscr = MmpcGainBlock<KIND, N>::ON ? gscr + (size_t)b * MmpcGainBlock<KIND, N>::total : nullptr;
         if (OPS == 2 && tick) io.tick = tick + b;   // the clock is indexed by instance row, like every per-instance array
+        io.scale_max_grad = scale_max_grad; if (scale_out) io.scale_out = scale_out + b;   // (objective scaling; by instance row too)
         mmpc_solve_fast<KIND, N, MC, CONT, OPS>(P, io, lds);
         if (!CONT || !resume_count) break;      // (one instance per workgroup except in a continuation launch)
         __builtin_amdgcn_s_barrier();           // the next instance reuses the LDS block
@@ -261,10 +266,10 @@ __global__ void mmpc_cold_xguess(int B, int NS, int NX, int clip, const MmpcPara
 // the signature of mmpc_solve_kernel<> and mmpc_solve_kernel_static<>, and that of mmpc_fast_kernel<>
 typedef void (*mmpc_gen_fn)(const MmpcParams *, int, const double *, const double *, const double *, const double *, const double *,
                             const double *, double *, double *, double *, int *, int *, double *, double *, const int *, double *, int,
-                            const long long *);
+                            const long long *, double, double *);
 typedef void (*mmpc_fast_fn)(const MmpcParams *, int, const double *, const double *, const double *, const double *, const double *,
                              const double *, double *, double *, double *, int *, int *, double *, double *, const int *, int, double *,
-                             int, const int *, const int *, double *, double *, int, const long long *);
+                             int, const int *, const int *, double *, double *, int, const long long *, double, double *);
 
 struct mmpc_handle_s {
     mmpc_config cfg;
@@ -275,6 +280,8 @@ struct mmpc_handle_s {
     mmpc_gen_fn gen_fn;     // generic: mmpc_solve_kernel<kind>, or the shape's static-LDS instantiation (MMPC_STATIC_LIST)
     int gen_dyn_lds;        // dynamic LDS of a gen_fn launch: lds_bytes, or 0 for a static-LDS instantiation
     const long long *d_tick;   // obs_per_stage = 2: the registered clock [max_batch] (mmpc_set_obstacle_clock; null: tick 0)
+    double scale_max_grad;     // objective scaling (mmpc_set_objective_scaling): nlp_scaling_max_gradient, 0 = off (the default)
+    double *d_scale_out;       // ... and the registered array of the instances' factors [max_batch] (null: not wanted)
     mmpc_fast_fn fast_fn[2];   // specialised [CONT] for the handle's obs_per_stage; null: (kind, N, M) has none (MMPC_FAST_LIST) or L > 0
     int fast_lds_bytes;
     int per_cu, fast_per_cu;   // resident workgroups (= problems) per CU the runtime reports for the two kernels
@@ -607,10 +614,12 @@ static int launch(mmpc_handle h, int B, const MmpcBatch &a, hipStream_t st, cons
                            h->dp, B, a.x_init, a.traj, a.uref, a.ulast, a.xguess, a.obs, a.X, a.U, a.s, a.status, a.iters, a.cost, a.err,
                            resume ? h->d_list : order, resume ? 0 : h->budget, cont ? h->d_state : (double *)nullptr,
                            cont ? h->state_doubles : 0, resume ? h->d_count : (const int *)nullptr,
-                           resume ? (const int *)nullptr : ucount, h->d_gscr, h->d_soc, h->soc_doubles, h->d_tick);
+                           resume ? (const int *)nullptr : ucount, h->d_gscr, h->d_soc, h->soc_doubles, h->d_tick,
+                           h->scale_max_grad, h->d_scale_out);
     } else
         hipLaunchKernelGGL(h->gen_fn, dim3(B), dim3(MMPC_WAVE), h->gen_dyn_lds, st, h->dp, B, a.x_init, a.traj, a.uref, a.ulast,
-                           a.xguess, a.obs, a.X, a.U, a.s, a.status, a.iters, a.cost, a.err, order, h->d_soc, h->soc_doubles, h->d_tick);
+                           a.xguess, a.obs, a.X, a.U, a.s, a.status, a.iters, a.cost, a.err, order, h->d_soc, h->soc_doubles, h->d_tick,
+                           h->scale_max_grad, h->d_scale_out);
     HIPCHK(h, hipGetLastError());
     if (use_fast && h->budget > 0 && !resume) {
         // who is suspended: compacted list for mmpc_resume_batch_device
@@ -702,6 +711,18 @@ extern "C" int mmpc_set_obstacle_clock(mmpc_handle h, const long long *d_tick) {
     // (the kernels read the array at launch time: wait for the handle's launches in flight before the pointer they were given goes)
     if (h->ev_valid) HIPCHK(h, hipEventSynchronize(h->ev));
     h->d_tick = d_tick;
+    return MMPC_OK;
+}
+
+extern "C" int mmpc_set_objective_scaling(mmpc_handle h, double max_gradient, double *d_scale_out) {
+    if (!h) return MMPC_E_ARG;
+    if (!(max_gradient >= 0.0) || !(max_gradient <= 1.79769313486231570815e308))   // (negative, NaN, infinite)
+        return fail(h, MMPC_E_ARG, "mmpc_set_objective_scaling: %s%s", "max_gradient must be 0 (off) or a positive finite number");
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    // (the kernels write d_scale_out: wait for the handle's launches in flight before the pointer they were given goes)
+    if (h->ev_valid) HIPCHK(h, hipEventSynchronize(h->ev));
+    h->scale_max_grad = max_gradient;
+    h->d_scale_out = max_gradient > 0.0 ? d_scale_out : nullptr;
     return MMPC_OK;
 }
 

@@ -12,6 +12,7 @@
 #define MMPC_LANE_XOR16(field) (ls_all[lane ^ 16].field)
 #define MMPC_LANE_LOWER16(field) (ls_all[lane & ~16].field)
 #define MMPC_FW_SLOTS 2
+#define MMPC_UNIFORM(x) (x)
 #define MMPC_WAVE_ANY(x) (x)     // (a flag declared outside the lane loop has been or-ed / min-ed over the lanes by the loop itself)
 #define MMPC_FW_SLOT(k) ((k) & 1)
 #define LANES_END_REG }
@@ -22,6 +23,7 @@
 #define MMPC_LANE_XOR16(field) mmpc_xor16_f64(ls_one.field, lane)
 #define MMPC_LANE_LOWER16(field) mmpc_lower16_f64(ls_one.field)
 #define MMPC_FW_SLOTS 1
+#define MMPC_UNIFORM(x) mmpc_readlane_f64((x), 0)   // a value every lane holds alike, moved to scalar registers (it then costs a long-lived solve no vector registers)
 #define MMPC_WAVE_ANY(x) (__builtin_amdgcn_ballot_w64(x) != 0ull)   // true in every lane if the flag is set in any
 #define MMPC_FW_SLOT(k) 0
 #define LANES_END_REG }      // end of a phase whose results travel in registers only: no LDS ordering to enforce

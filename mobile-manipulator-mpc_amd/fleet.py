@@ -28,13 +28,18 @@ a clock of per-robot tick counts (mmpc_set_obstacle_clock) instead of the (B, N+
 form the table's centres where they read them, so every number is the table mode's, bit for bit, and no table is allocated,
 written or streamed anywhere.  The clock is the tick tensor the drivers advance anyway (in place; run_async keeps one per buffer
 set, filled next to x_in, so that a continuation on the side stream reads the ticks of its own launch).
+
+nlp_scaling="gradient-based" (with nlp_scaling_max_gradient, default 100): IPOPT's objective scaling on every handle of the fleet
+(mmpc_set_objective_scaling; sub-fleets of run_groups and the handles of run_async included).  None: the engine's default, off.
 """
 import numpy as np
 
 
 class DeviceFleet:
-    def __init__(self, mm, x0, glob, obs0, vel, N=30, device=0, dt=0.1, handles=3, fused=False, warm_start="reference", obstacles="table"):
+    def __init__(self, mm, x0, glob, obs0, vel, N=30, device=0, dt=0.1, handles=3, fused=False, warm_start="reference", obstacles="table",
+                 nlp_scaling=None, nlp_scaling_max_gradient=100.0):
         import torch
+        self.nlp_scaling, self.nlp_scaling_max_gradient = nlp_scaling, nlp_scaling_max_gradient
         if obstacles not in ("table", "motion"):
             raise ValueError("obstacles must be 'table' or 'motion', not %r" % (obstacles,))
         self.obstacles = obstacles
@@ -49,7 +54,8 @@ class DeviceFleet:
         self.dev = torch.device("cuda", device)
         B, M = self.B, self.M
         mk = lambda: mm.MPCWholeBody(mm.MobileManipulator(dt), [], [], N=N, max_batch=max(B, 1), device=device, n_obstacles=M,
-                                     obs_per_stage="motion" if self.motion else True)
+                                     obs_per_stage="motion" if self.motion else True, nlp_scaling=nlp_scaling,
+                                     nlp_scaling_max_gradient=nlp_scaling_max_gradient)
         # [0]: lock step (plain kernel); [1], [2]: the two alternating handles of run_async, created on its first call.  A handle owns
         # max_batch rows of device state: staging, warm start, the second-order-correction scratch and - long horizons - the gain
         # blocks (mmpc_create: about 0.5 MB per robot at N = 30, M = 8)
@@ -217,7 +223,8 @@ class DeviceFleet:
             for g in range(G):
                 lo, hi = sharding.shard_bounds(self.B, G, g)
                 sub = DeviceFleet(mm, self.x0[lo:hi], self.glob[lo:hi], self.obs0[lo:hi], self.vel[lo:hi], N=self.N, device=self.dev.index, dt=self.dt,
-                                  handles=1, fused=self.fused, warm_start=self.warm_start, obstacles=self.obstacles)
+                                  handles=1, fused=self.fused, warm_start=self.warm_start, obstacles=self.obstacles,
+                                  nlp_scaling=self.nlp_scaling, nlp_scaling_max_gradient=self.nlp_scaling_max_gradient)
                 # (priority: lower number = served first; the last group runs at the default priority)
                 pr = (max(hi_pr, min(lo_pr, 0 - (G - 1 - g))) if hi_pr < 0 else 0) if priority else 0
                 self._groups.append((lo, hi, sub, torch.cuda.Stream(device=self.dev, priority=pr)))

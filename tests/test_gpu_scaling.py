@@ -1,0 +1,258 @@
+"""GPU (MI355X): the objective scaling (mmpc_set_objective_scaling; IPOPT's nlp_scaling_method = gradient-based) through the C ABI,
+on the inputs of tests/test_scaling_cpu.py: the factor against numpy, the solve against the C oracle's solve of the instance
+with its weights times the factor, against the host emulation of the kernels, and - bit for bit - against the device's own
+solve of that twin with the option off.  The specialised shapes run on handles made by the controller classes."""
+import numpy as np
+import pytest
+
+from oracle import nlp
+
+import cert_pool
+import scaling_helper as sh
+import test_scaling_cpu as T
+import tick_emu_helper as H
+
+pytestmark = pytest.mark.gpu
+G = sh.G_IPOPT
+CASES = T.CASES
+FAST_CASES = [c for c in CASES if c[0] == "fast"]
+KEYS = sh.BIT_KEYS + ("cost",)
+
+
+@pytest.fixture(autouse=True)
+def _scaling_abi(mm):
+    """a library without the option is found out from the missing symbol, before anything is launched"""
+    assert hasattr(mm._capi.lib(), "mmpc_set_objective_scaling"), "libmmpc.so has no mmpc_set_objective_scaling"
+    assert hasattr(mm._capi.Engine, "set_objective_scaling")
+
+
+def _dev(a):
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(a)).to(torch.device("cuda", 0))
+
+
+def _ctrl(mm, par, M, B, **kw):
+    """a controller of the case's kind (the pose-reference and the dense-weight cases included): its handle is ctrl._engine"""
+    if par.kind == "base":
+        xl = par.xlim[:, [0, 1, 3, 4, 5]]
+        c = mm.MPCBase(mm.Base(par.dt), [], N=par.N, Q=par.Q, P=par.P, R=par.R, M=np.diag([par.S]), ulim=par.ulim, xlim=xl, max_batch=B, n_obstacles=M, **kw)
+    elif getattr(par, "pose_ref", False):
+        c = mm.MPCWholeBodyPoseRef(mm.MobileManipulator(par.dt), [], N=par.N, Q=par.Q, P=par.P, R=par.R, S=np.diag([par.S]), W=par.W,
+                                   ulim=par.ulim, xlim=par.xlim, dulim=par.dulim, max_batch=B, n_obstacles=M, **kw)
+    else:
+        c = mm.MPCWholeBody(mm.MobileManipulator(par.dt), [], [], N=par.N, Q=par.Q, P=par.P, R=par.R, S=np.diag([par.S]), W=par.W,
+                            ulim=par.ulim, xlim=par.xlim, dulim=par.dulim, max_batch=B, n_obstacles=M, **kw)
+    return c
+
+
+def _weights(eng, par):
+    eng.set_weights(Q=par.Q, R=par.R, P=par.P, S=par.S, W=par.W)
+
+
+class _Run:
+    """the device tensors of a case (made once per handle) and its launches"""
+
+    def __init__(self, eng, d):
+        import torch
+        self.eng, self.B = eng, d["x_init"].shape[0]
+        self.t = {k: _dev(d[k]) for k in ("x_init", "traj_ref", "u_ref", "u_last", "obs")}
+        self.xg = _dev(d["x_guess"]) if d.get("x_guess") is not None else None
+        if d.get("u_guess") is not None:
+            eng.set_warm_start(_dev(d["u_guess"]), 1.0)
+        self.scale = torch.full((eng.max_batch,), -1.0, dtype=torch.float64, device="cuda:0")
+
+    def solve(self, max_gradient, **kw):
+        import torch
+        self.scale.fill_(-1.0)
+        self.eng.set_objective_scaling(max_gradient, self.scale)
+        t = self.t
+        r = self.eng.solve_batch_device(t["x_init"], t["traj_ref"], t["u_ref"], t["u_last"], t["obs"], x_guess=self.xg, **kw)
+        torch.cuda.synchronize()
+        out = {k: v.cpu().numpy() for k, v in r.items()}
+        out["scale"] = self.scale.cpu().numpy()[:self.B]
+        return out, r
+
+
+_gpu = {}
+
+
+def _case(mm, case):
+    """the CPU test's case (inputs, numpy factors, emulation outputs) and, once, its device solves with the option on and off"""
+    c = T._case(case)
+    if case not in _gpu:
+        par, d = c["par"], c["d"]
+        ctrl = _ctrl(mm, par, d["obs"].shape[1], d["x_init"].shape[0])
+        run = _Run(ctrl._engine, d)
+        _gpu[case] = dict(ctrl=ctrl, run=run, on=run.solve(G)[0], off=run.solve(0.0)[0])
+    return c, _gpu[case]
+
+
+@pytest.mark.parametrize("case", CASES, ids=str)
+def test_factor_equals_numpy_and_kernel_choice(mm, case):
+    c, g = _case(mm, case)
+    assert np.abs(g["on"]["scale"] / c["sig"] - 1).max() <= 1e-13
+    assert ((g["on"]["scale"] == 1) == (c["sig"] == 1)).all()
+    assert (g["off"]["scale"] == -1).all()          # off: nothing is written
+    eng, (k, N, M) = g["ctrl"]._engine, (sh.kind_id(c["par"]), c["par"].N, c["d"]["obs"].shape[1])
+    if c["fast"]:
+        assert eng.lds_bytes == 8 * sh.fast_lds_doubles(k, N, M, 0)      # the specialised kernel runs
+    else:
+        assert eng.lds_bytes == 8 * sh.lds_doubles(k, N, M, 0)
+
+
+@pytest.mark.parametrize("case", CASES, ids=str)
+def test_parity_with_the_oracle_and_the_emulation(mm, case):
+    c, g = _case(mm, case)
+    r, e = g["on"], c["on"]
+    o = sh.oracle_scaled(c["par"], c["d"], c["sig"])
+    print("iters gpu", r["iters"], "emu", e["iters"], "oracle", o["iters"])
+    print("gpu - oracle: dX %.2e dU %.2e ds %.2e cost %.2e; gpu - emu: dX %.2e cost %.2e" % (
+        np.abs(o["X"] - r["X"]).max(), np.abs(o["U"] - r["U"]).max(), np.abs(o["s"] - r["s"]).max(),
+        np.abs(r["cost"] / (o["cost"] / c["sig"]) - 1).max(), np.abs(e["X"] - r["X"]).max(), np.abs(r["cost"] / e["cost"] - 1).max()))
+    assert (o["status"] == 0).all() and (r["status"] == 0).all()
+    assert (np.abs(o["iters"] - r["iters"]) <= 2).mean() > 0.8
+    assert np.abs(o["X"] - r["X"]).max() < 1e-6 and np.abs(o["U"] - r["U"]).max() < 1e-6 and np.abs(o["s"] - r["s"]).max() < 1e-6
+    assert np.abs(r["cost"] / (o["cost"] / c["sig"]) - 1).max() <= 1e-9
+    # the device against the host build of the same kernel: the rule of test_long_horizon_kernel_against_its_host_build
+    assert (r["iters"] == e["iters"]).mean() >= 0.9, (r["iters"], e["iters"])
+    same = np.abs(r["cost"] / e["cost"] - 1) < 1e-6
+    assert same.mean() >= 0.95 and np.abs(r["X"][same] - e["X"][same]).max() < 1e-6
+
+
+@pytest.mark.parametrize("case", FAST_CASES, ids=str)
+def test_twin_bitwise(mm, case):
+    """instance b with the option on = instance b alone, option off, Q, P, R, W, S x sigma_b (sigma_b read from scale_out)"""
+    c, g = _case(mm, case)
+    par, d, on = c["par"], c["d"], g["on"]
+    tw = _ctrl(mm, par, d["obs"].shape[1], 1)
+    changed = 0
+    for b in range(d["x_init"].shape[0]):
+        sg = on["scale"][b]
+        _weights(tw._engine, sh.scaled_par(par, sg))
+        t = _Run(tw._engine, sh.instance(d, b)).solve(0.0)[0]
+        sh.assert_bitwise({k: on[k][b:b + 1] for k in sh.BIT_KEYS}, t, what="instance %d" % b)
+        assert abs(on["cost"][b] / (t["cost"][0] / sg) - 1) <= 1e-12
+        changed += int(on["iters"][b] != g["off"]["iters"][b])
+    assert changed > 0      # the scaled solve is another solve than the unscaled one
+
+
+@pytest.mark.parametrize("case", CASES, ids=str)
+def test_factor_one_is_the_unscaled_solve_bitwise(mm, case):
+    c, g = _case(mm, case)
+    r = g["run"].solve(1e30)[0]
+    assert (r["scale"] == 1).all()
+    sh.assert_bitwise(r, g["off"], keys=KEYS, what="sigma = 1")
+
+
+@pytest.mark.parametrize("shape,budget", [((0, 20, 5), 7), ((1, 15, 3), 3)], ids=str)
+def test_budgeted_and_resumed_equals_uninterrupted(mm, shape, budget):
+    c, g = _case(mm, ("fast",) + shape)
+    run, eng = g["run"], g["ctrl"]._engine
+    eng.set_iteration_budget(budget)
+    try:
+        first, out = run.solve(G)
+        nsusp = eng.suspended_count()
+        assert nsusp >= 8 and int((first["status"] == 3).sum()) == nsusp
+        run.scale.fill_(-1.0)
+        t = run.t
+        eng.resume_batch_device(t["x_init"], t["traj_ref"], t["u_ref"], t["u_last"], t["obs"], out)
+        import torch
+        torch.cuda.synchronize()
+        r = {k: v.cpu().numpy() for k, v in out.items()}
+        sh.assert_bitwise(r, g["on"], keys=KEYS, what="budget %d + continuation" % budget)
+        # the continuation reports the factor of the solves it continued, and of those alone
+        sc = run.scale.cpu().numpy()
+        susp = first["status"] == 3
+        assert np.array_equal(sc[susp], g["on"]["scale"][susp]) and (sc[~susp] == -1).all()
+    finally:
+        eng.set_iteration_budget(0)
+
+
+def test_list_launch_leaves_the_other_rows_alone(mm):
+    import torch
+    c, g = _case(mm, ("fast", 0, 20, 3))
+    run, full = g["run"], g["on"]
+    B, N = run.B, c["par"].N
+    rows = np.random.default_rng(3).permutation(B)[:B // 2].astype(np.int32)
+    f = lambda *s: torch.full(s, -7.0, dtype=torch.float64, device="cuda:0")
+    i = lambda *s: torch.full(s, -7, dtype=torch.int32, device="cuda:0")
+    out = dict(X=f(B, N + 1, 9), U=f(B, N, 5), s=f(B, N + 1), status=i(B), iters=i(B), cost=f(B), err=f(B))
+    lst = run.solve(G, out=out, rows=(_dev(rows), _dev(np.array([len(rows)], np.int32))))[0]
+    rest = np.setdiff1d(np.arange(B), rows)
+    for key in KEYS:
+        assert np.array_equal(lst[key][rows], full[key][rows]), key
+        assert (lst[key][rest] == -7).all(), key
+    assert np.array_equal(lst["scale"][rows], full["scale"][rows]) and (lst["scale"][rest] == -1).all()
+
+
+def test_ipopt_certificate_of_the_scaled_problem(mm):
+    """IPOPT's termination test, with multipliers that are not the solver's, for the NLP the option makes of each instance"""
+    c, g = _case(mm, ("fast", 0, 20, 5))
+    par, d, r = c["par"], c["d"], g["on"]
+    items = []
+    for b in range(d["x_init"].shape[0]):
+        prob = nlp.Problem(sh.scaled_par(par, r["scale"][b]), nlp.clip_x_init(par, d["x_init"][b]), d["traj_ref"][b], d["u_ref"][b], d["u_last"][b], d["obs"][b])
+        items.append((prob, r["X"][b], r["U"][b], r["s"][b]))
+    e0 = np.array([k["E0"] for k in cert_pool.certify(items, label="scaled certificates")])
+    print("certificate E0 of the scaled problems: max %.2e" % e0.max(), np.round(e0 * 1e9, 2))
+    assert e0.max() <= 1.5e-8, e0
+
+
+def test_occupancy_setter_errors_and_controller_keyword(mm):
+    for case in FAST_CASES + [("generic", "wb", 6, 2)]:
+        c, g = _case(mm, case)
+        eng = g["ctrl"]._engine
+        eng.set_objective_scaling(0.0)
+        off = (eng.lds_bytes, eng.problems_per_cu)
+        eng.set_objective_scaling(G)
+        assert (eng.lds_bytes, eng.problems_per_cu) == off, case
+    for bad in (-1.0, float("nan"), float("inf")):
+        with pytest.raises(RuntimeError, match=r"mmpc_set_objective_scaling failed \(-1\)"):
+            eng.set_objective_scaling(bad)
+    with pytest.raises(ValueError, match="nlp_scaling"):
+        _ctrl(mm, c["par"], 2, 1, nlp_scaling="equilibration-based")
+    # the controller keyword is the setter
+    for case in (("fast", 0, 20, 3), ("fast", 1, 15, 3), ("generic", "pose", 6, 2)):
+        c, g = _case(mm, case)
+        d = c["d"]
+        kw = _ctrl(mm, c["par"], d["obs"].shape[1], d["x_init"].shape[0], nlp_scaling="gradient-based", nlp_scaling_max_gradient=G)
+        plain = _ctrl(mm, c["par"], d["obs"].shape[1], d["x_init"].shape[0], nlp_scaling="none")
+        xi = d["x_init"] if c["par"].kind == "base" else np.clip(d["x_init"], c["par"].xlim[0], c["par"].xlim[1])
+        a, b = (k.solve_batch(xi, d["traj_ref"], d["u_ref"], d["obs"]) for k in (kw, plain))
+        for key in ("X", "U", "s", "status", "iters", "cost"):
+            assert a[key].tobytes() == g["on"][key].tobytes() and b[key].tobytes() == g["off"][key].tobytes(), (case, key)
+
+
+def test_fleet_with_scaling(mm):
+    import torch
+    from oracle import synth
+    B, Tn, N, M = 8, 3, 30, 8
+    d = synth.make_batch(B, N=N, M=M, config_id=5, moving=True)
+    par = nlp.WholeBodyParams(N=N)
+    fleet = mm.DeviceFleet(mm, np.clip(d["x_init"], par.xlim[0], par.xlim[1]), _dev(H.straight_plan(d["traj_ref"], N)), d["obs"], d["obs_vel"],
+                           N=N, fused=True, nlp_scaling="gradient-based")
+    res = {}
+    ticks = fleet._lockstep_ticks(Tn, res)
+    next(ticks)
+    torch.cuda.synchronize()
+    F = fleet._fin
+    x_in, loc, obs = F["x_in"].clone(), F["loc"].clone(), F["obs"].clone()
+    tick0 = {k: v.cpu().numpy() for k, v in fleet._fsets[0].items()}
+    for _ in ticks:
+        pass
+    torch.cuda.synchronize()
+    assert bool(res["all_converged"]), res["iters"]
+    # tick 0 = the engine-level scaled solve of the same inputs; without the option it is another solve
+    ctrl = _ctrl(mm, par, M, B, obs_per_stage=True)
+    eng = ctrl._engine
+    scale = torch.full((B,), -1.0, dtype=torch.float64, device="cuda:0")
+    zero = torch.zeros((B, N, 5), dtype=torch.float64, device="cuda:0")
+    eng.set_objective_scaling(G, scale)
+    r = eng.solve_batch_device(x_in, loc, zero, zero, obs)
+    torch.cuda.synchronize()
+    sh.assert_bitwise({k: v.cpu().numpy() for k, v in r.items()}, tick0, keys=KEYS, what="fleet tick 0")
+    assert (scale.cpu().numpy() < 1).all()
+    eng.set_objective_scaling(0.0)
+    r = eng.solve_batch_device(x_in, loc, zero, zero, obs)
+    torch.cuda.synchronize()
+    assert not np.array_equal(r["iters"].cpu().numpy(), tick0["iters"])
