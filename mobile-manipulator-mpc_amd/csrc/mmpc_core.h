@@ -345,6 +345,13 @@ MMPC_DEV double mmpc_min(double a, double b) { return a < b ? a : b; }
 // ---- objective scaling (opt-in; IPOPT's nlp_scaling_method = gradient-based, IpGradientScaling): the factor of the objective from
 // g = the max-norm of its gradient at the starting point and G = nlp_scaling_max_gradient; 1e-8 is IPOPT's nlp_scaling_min_value.
 // (A NaN g fails the comparison: factor 1 - the solve reports the NaN itself, status 2.)
+// (R2 + W2) sigma as the caller who multiplies the weights by sigma himself would hand it over, R2 sigma + W2 sigma with every
+// operation rounded on its own: the scaled solve is then the solve of the weights times sigma bit for bit also where R and W are
+// both non-zero in one entry ((R2 + W2) sigma rounds differently)
+MMPC_DEV double mmpc_scaled_rw2(double r2, double w2, double sigma) {
+#pragma clang fp contract(off)
+    return r2 * sigma + w2 * sigma;
+}
 MMPC_DEV double mmpc_scale_factor(double g, double G) {
     if (!(g > G)) return 1.0;
     const double f = G / g;
@@ -796,7 +803,8 @@ MMPC_DEV void mmpc_solve_one(const MmpcParams &P, const MmpcIO io, double *lds M
         LANES_END
         sigma = MMPC_UNIFORM(mmpc_scale_factor(MMPC_GRED_MAX(RED), io.scale_max_grad));
         LANES_BEGIN
-        for (int i = lane; i < MMPC_W_XLIM; i += MMPC_WAVE) WTS[i] *= sigma;
+        for (int i = lane; i < MMPC_W_XLIM; i += MMPC_WAVE)
+            WTS[i] = (i >= MMPC_W_RW2 && i < MMPC_W_R2) ? mmpc_scaled_rw2(P.R2[i - MMPC_W_RW2], P.W2[i - MMPC_W_RW2], sigma) : WTS[i] * sigma;
         if (lane == 0 && io.scale_out) *io.scale_out = sigma;
         LANES_END
         Sw = MMPC_UNIFORM(P.S * sigma);

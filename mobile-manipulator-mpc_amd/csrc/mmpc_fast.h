@@ -656,7 +656,8 @@ MMPC_DEV void mmpc_solve_fast(const MmpcParams &P, const MmpcIO io, double *lds 
         }
         sigma = MMPC_UNIFORM(sigma);
         LANES_BEGIN
-        for (int i = lane + MMPC_C_WQ; i < MMPC_C_SCALE; i += MMPC_WAVE) CST[i] *= sigma;
+        for (int i = lane + MMPC_C_WQ; i < MMPC_C_SCALE; i += MMPC_WAVE)
+            CST[i] = i >= MMPC_C_RW2 ? mmpc_scaled_rw2(P.R2[i - MMPC_C_RW2], P.W2[i - MMPC_C_RW2], sigma) : CST[i] * sigma;
         if (lane == 0) { CST[MMPC_C_SCALE] = sigma; if (io.scale_out) *io.scale_out = sigma; }
         LANES_END
         Sw = MMPC_UNIFORM(P.S * sigma);

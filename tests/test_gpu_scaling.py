@@ -100,9 +100,8 @@ def test_factor_equals_numpy_and_kernel_choice(mm, case):
         assert eng.lds_bytes == 8 * sh.lds_doubles(k, N, M, 0)
 
 
-@pytest.mark.parametrize("case", CASES, ids=str)
-def test_parity_with_the_oracle_and_the_emulation(mm, case):
-    c, g = _case(mm, case)
+def _assert_oracle(c, g):
+    """the device against the C oracle's solve of the weights times sigma (and the numbers of the host build, printed)"""
     r, e = g["on"], c["on"]
     o = sh.oracle_scaled(c["par"], c["d"], c["sig"])
     print("iters gpu", r["iters"], "emu", e["iters"], "oracle", o["iters"])
@@ -113,16 +112,25 @@ def test_parity_with_the_oracle_and_the_emulation(mm, case):
     assert (np.abs(o["iters"] - r["iters"]) <= 2).mean() > 0.8
     assert np.abs(o["X"] - r["X"]).max() < 1e-6 and np.abs(o["U"] - r["U"]).max() < 1e-6 and np.abs(o["s"] - r["s"]).max() < 1e-6
     assert np.abs(r["cost"] / (o["cost"] / c["sig"]) - 1).max() <= 1e-9
+
+
+def _assert_parity(c, g):
+    _assert_oracle(c, g)
+    r, e = g["on"], c["on"]
     # the device against the host build of the same kernel: the rule of test_long_horizon_kernel_against_its_host_build
     assert (r["iters"] == e["iters"]).mean() >= 0.9, (r["iters"], e["iters"])
     same = np.abs(r["cost"] / e["cost"] - 1) < 1e-6
     assert same.mean() >= 0.95 and np.abs(r["X"][same] - e["X"][same]).max() < 1e-6
 
 
-@pytest.mark.parametrize("case", FAST_CASES, ids=str)
-def test_twin_bitwise(mm, case):
-    """instance b with the option on = instance b alone, option off, Q, P, R, W, S x sigma_b (sigma_b read from scale_out)"""
-    c, g = _case(mm, case)
+@pytest.mark.parametrize("case", CASES, ids=str)
+def test_parity_with_the_oracle_and_the_emulation(mm, case):
+    _assert_parity(*_case(mm, case))
+
+
+def _assert_twin(mm, c, g, differs="iters"):
+    """instance b with the option on = instance b alone, option off, Q, P, R, W, S x sigma_b (sigma_b read from scale_out);
+    differs: what tells the scaled solve from the unscaled one - the iteration counts, or "X" where the solves are too short for that"""
     par, d, on = c["par"], c["d"], g["on"]
     tw = _ctrl(mm, par, d["obs"].shape[1], 1)
     changed = 0
@@ -132,8 +140,13 @@ def test_twin_bitwise(mm, case):
         t = _Run(tw._engine, sh.instance(d, b)).solve(0.0)[0]
         sh.assert_bitwise({k: on[k][b:b + 1] for k in sh.BIT_KEYS}, t, what="instance %d" % b)
         assert abs(on["cost"][b] / (t["cost"][0] / sg) - 1) <= 1e-12
-        changed += int(on["iters"][b] != g["off"]["iters"][b])
+        changed += int(on[differs][b].tobytes() != g["off"][differs][b].tobytes())
     assert changed > 0      # the scaled solve is another solve than the unscaled one
+
+
+@pytest.mark.parametrize("case", FAST_CASES, ids=str)
+def test_twin_bitwise(mm, case):
+    _assert_twin(mm, *_case(mm, case))
 
 
 @pytest.mark.parametrize("case", CASES, ids=str)
@@ -256,3 +269,173 @@ def test_fleet_with_scaling(mm):
     r = eng.solve_batch_device(x_in, loc, zero, zero, obs)
     torch.cuda.synchronize()
     assert not np.array_equal(r["iters"].cpu().numpy(), tick0["iters"])
+
+
+# ---- the gradient term by term (tests/test_scaling_cpu.py: test_onehot_factor), through the C ABI with max_iter = 1
+# generic: the specialised shape on the generic kernel (MMPC_FORCE_GENERIC, read when the handle is created)
+ONEHOT_GPU = ([(s, False, v, False, g) for s in sh.ONEHOT_SHAPES for v in sh.ONEHOT_VARIANTS for g in (False, True)]
+              + [(s, False, "plain", mode, False) for s in sh.ONEHOT_SHAPES for mode in (True, "motion")]       # (other kernels: the mode is a compile-time constant)
+              + [(s, True, v, False, True) for s in sh.ONEHOT_DENSE for v in sh.ONEHOT_VARIANTS]
+              + [(("pose", 6, 2), dense, v, False, True) for dense in (False, True) for v in ("plain", "uguess")])
+
+
+@pytest.mark.parametrize("shape,dense,variant,mode,generic", ONEHOT_GPU, ids=str)
+def test_onehot_factor(mm, monkeypatch, shape, dense, variant, mode, generic):
+    """every entry of grad f(w0) decides the factor of one instance; mode: the obstacle mode of the handle (the clock stays NULL)"""
+    par, d, sig, _ = T.onehot_case(*shape, dense, variant)
+    B, M = d["x_init"].shape[0], d["obs"].shape[1]
+    if generic:
+        monkeypatch.setenv("MMPC_FORCE_GENERIC", "1")
+    ctrl = _ctrl(mm, par, M, B, max_iter=1, **(dict(obs_per_stage=mode) if mode else {}))
+    monkeypatch.delenv("MMPC_FORCE_GENERIC", raising=False)
+    eng = ctrl._engine
+    _weights(eng, par)      # (W of the base kind too, which its controller leaves at zero)
+    r = _Run(eng, dict(d, obs=sh.obs_in_mode(d["obs"], par.N, mode))).solve(G)[0]
+    T.onehot_assert(r["scale"], r["status"], sig)
+    k, ops = sh.kind_id(par), {False: 0, True: 1, "motion": 2}[mode]
+    if generic:
+        assert eng.lds_bytes == 8 * sh.lds_doubles(k, par.N, M, 0)                 # the generic kernel ran
+    else:
+        assert eng.lds_bytes == 8 * sh.fast_lds_doubles(k, par.N, M, ops)      # the specialised kernel of this mode ran
+
+
+# ---- full solves whose factor another term than Q (x0 - x_ref_k) decides (sh.decider_inputs)
+_gpu_dec = {}
+
+
+def _decider(mm, case, generic=False):
+    """the CPU test's case and, once, its device solves with the option on and off; generic: the caller has set MMPC_FORCE_GENERIC
+    (read when a handle is created), so the handle runs the generic kernel whatever the shape"""
+    c = T.decider_case(case)
+    key = (case, generic)
+    if key not in _gpu_dec:
+        par, d = c["par"], c["d"]
+        ctrl = _ctrl(mm, par, d["obs"].shape[1], d["x_init"].shape[0])
+        _weights(ctrl._engine, par)
+        run = _Run(ctrl._engine, d)
+        _gpu_dec[key] = dict(ctrl=ctrl, run=run, on=run.solve(G)[0], off=run.solve(0.0)[0])
+    return c, _gpu_dec[key]
+
+
+@pytest.mark.parametrize("case", T.DECIDERS, ids=str)
+def test_decider_factor_and_oracle(mm, case):
+    c, g = _decider(mm, case)
+    assert np.abs(g["on"]["scale"] / c["sig"] - 1).max() <= 1e-13
+    assert ((g["on"]["scale"] == 1) == (c["sig"] == 1)).all()
+    eng, (k, N, M) = g["ctrl"]._engine, (sh.kind_id(c["par"]), c["par"].N, c["d"]["obs"].shape[1])
+    assert eng.lds_bytes == 8 * (sh.fast_lds_doubles(k, N, M, 0) if c["fast"] else sh.lds_doubles(k, N, M, 0))
+    # (the oracle comparison alone: these solves take 6 to 8 iterations and leave with an error of 1e-9 against a tolerance of
+    #  1e-8 one barrier step earlier or later - where the last step falls can differ between the device's fused multiply-adds and
+    #  the host build, which the oracle comparison allows for and the equal-count rule does not.  Seen in one device run: in
+    #  ("R", 1, 15, 3) and ("W", 1, 15, 3) one instance of eight ended at 7 iterations on the device and the oracle, at 9 and 11 on
+    #  the host build - 0.875 of the batch equal, against the rule's 0.9)
+    _assert_oracle(c, g)
+    same = np.abs(g["on"]["cost"] / c["on"]["cost"] - 1) < 1e-6
+    assert same.mean() >= 0.95 and np.abs(g["on"]["X"][same] - c["on"]["X"][same]).max() < 1e-6
+
+
+@pytest.mark.parametrize("kern,case", T.DECIDER_TWINS, ids=str)
+def test_decider_twin_bitwise(mm, monkeypatch, kern, case):
+    """the specialised shapes on both kernels, the ("wb", 6, 2) cases on the generic one; the twin's handle is made on the same kernel"""
+    if kern == "generic":
+        monkeypatch.setenv("MMPC_FORCE_GENERIC", "1")
+    c, g = _decider(mm, case, kern == "generic")
+    eng, (k, N, M) = g["ctrl"]._engine, (sh.kind_id(c["par"]), c["par"].N, c["d"]["obs"].shape[1])
+    assert eng.lds_bytes == 8 * (sh.fast_lds_doubles(k, N, M, 0) if kern == "fast" else sh.lds_doubles(k, N, M, 0))
+    assert np.abs(g["on"]["scale"] / c["sig"] - 1).max() <= 1e-13
+    _assert_twin(mm, c, g, differs="X")
+
+
+def test_decider_budgeted_and_resumed_with_a_guess(mm):
+    """the factor travels through the save area together with a guess"""
+    import torch
+    case, budget = T.DECIDER_BUDGET
+    c, g = _decider(mm, case)
+    run, eng = g["run"], g["ctrl"]._engine
+    eng.set_iteration_budget(budget)
+    try:
+        first, out = run.solve(G)
+        nsusp = eng.suspended_count()
+        assert nsusp == run.B and int((first["status"] == 3).sum()) == nsusp
+        run.scale.fill_(-1.0)
+        t = run.t
+        eng.resume_batch_device(t["x_init"], t["traj_ref"], t["u_ref"], t["u_last"], t["obs"], out)
+        torch.cuda.synchronize()
+        r = {k: v.cpu().numpy() for k, v in out.items()}
+        sh.assert_bitwise(r, g["on"], keys=KEYS, what="budget %d + continuation" % budget)
+        assert np.array_equal(run.scale.cpu().numpy()[:run.B], g["on"]["scale"])
+    finally:
+        eng.set_iteration_budget(0)
+
+
+# ---- the host-pointer call's warm start: the second call starts at, and is scaled at, the first call's optimum
+@pytest.mark.parametrize("shape", [(0, 20, 3), (1, 15, 3)], ids=str)
+def test_host_pointer_warm_start(mm, shape):
+    c, g = _case(mm, ("fast",) + shape)
+    par, d = c["par"], c["d"]
+    B, M = d["x_init"].shape[0], d["obs"].shape[1]
+    kw = _ctrl(mm, par, M, B, nlp_scaling="gradient-based", nlp_scaling_max_gradient=G)
+    xi = d["x_init"] if par.kind == "base" else np.clip(d["x_init"], par.xlim[0], par.xlim[1])
+    first = kw.solve_batch(xi, d["traj_ref"], d["u_ref"], d["obs"])
+    second = kw.solve_batch(xi, d["traj_ref"], d["u_ref"], d["obs"])
+    conv = first["status"] == 0
+    assert conv.sum() * 2 >= B
+    # the device-pointer solve of the same instances with u_last = the first U (and, base kind, the first X as the X guess)
+    d2 = dict(d, u_last=first["U"])
+    if par.kind == "base":
+        d2["x_guess"] = first["X"]
+    r = _Run(_ctrl(mm, par, M, B)._engine, d2).solve(G)[0]
+    sig2 = sh.sigma_numpy(par, d2)[0]
+    assert np.abs(r["scale"][conv] / sig2[conv] - 1).max() <= 1e-13
+    for key in ("X", "U", "s", "status", "iters", "cost"):
+        assert second[key][conv].tobytes() == r[key][conv].tobytes(), (shape, key)
+    assert not np.array_equal(second["iters"], first["iters"])      # (the second call is another solve than the first)
+
+
+# ---- receding horizon: the factor at ticks >= 1 (tests/test_scaling_cpu.py: test_fleet_ticks_factor)
+@pytest.mark.parametrize("warm_start", ["shifted", "reference"])
+def test_fleet_ticks_factor(mm, warm_start):
+    """every tick's factor is numpy's at that tick's own starting point (u_last = the previous optimum; the shifted guess and its
+    roll-out when there are some), and the last tick is, bit for bit, the engine-level solve of its inputs on a second handle"""
+    import torch
+    par, x0, glob, obs0, vel = sh.fleet_plan()
+    B, N, M, Tn = (sh.FLEET[k] for k in "BNMT")
+    fleet = mm.DeviceFleet(mm, x0, _dev(glob), obs0, vel, N=N, fused=True, warm_start=warm_start, nlp_scaling="gradient-based")
+    scale = torch.full((B,), -1.0, dtype=torch.float64, device="cuda:0")
+    fleet.engs[0].set_objective_scaling(G, scale)
+    res, snaps = {}, []
+    zero = torch.zeros((B, N, 5), dtype=torch.float64, device="cuda:0")
+    ticks = fleet._fused_ticks(Tn, res)
+    for t in ticks:
+        torch.cuda.synchronize()
+        F = fleet._fin
+        warm = warm_start == "shifted" and t >= 1
+        snaps.append(dict(x_in=F["x_in"].clone(), loc=F["loc"].clone(), obs=F["obs"].clone(), prev=fleet._fsets[(t - 1) & 1]["U"].clone() if t else zero,
+                          ug=F["ug"].clone() if warm else None, xg=F["xg"].clone() if warm else None, scale=scale.clone(),
+                          out={k: v.clone() for k, v in fleet._fsets[t & 1].items()}))
+    torch.cuda.synchronize()
+    assert bool(res["all_converged"]), res["iters"]
+    decided = 0
+    h = lambda a: None if a is None else a.cpu().numpy()
+    for t, s in enumerate(snaps):
+        d = sh.tick_inputs(h(s["x_in"]), h(s["loc"]), h(s["obs"]), h(s["prev"]), h(s["ug"]), h(s["xg"]))
+        sig, sc = sh.sigma_numpy(par, d)[0], h(s["scale"])
+        print("tick", t, "sigma", np.round(sig, 4), "iters", h(s["out"]["iters"]))
+        assert np.abs(sc / sig - 1).max() <= 1e-13 and ((sc == 1) == (sig == 1)).all()
+        if t >= 1:
+            assert np.abs(d["u_last"]).max() > 0.1
+        if s["ug"] is not None:
+            decided += int(sh.guess_decides(par, d).sum())
+    if warm_start == "shifted":
+        assert decided > 0          # otherwise nothing here sees which point the factor was formed at
+    # the last tick on a second handle
+    s = snaps[-1]
+    eng = _ctrl(mm, par, M, B, obs_per_stage=True)._engine
+    if s["ug"] is not None:
+        eng.set_warm_start(s["ug"], 0.1)
+    sc2 = torch.full((B,), -1.0, dtype=torch.float64, device="cuda:0")
+    eng.set_objective_scaling(G, sc2)
+    r = eng.solve_batch_device(s["x_in"], s["loc"], zero, s["prev"], s["obs"], x_guess=s["xg"])
+    torch.cuda.synchronize()
+    sh.assert_bitwise({k: h(v) for k, v in r.items()}, {k: h(v) for k, v in s["out"].items()}, keys=KEYS, what="fleet tick %d" % (Tn - 1))
+    assert np.array_equal(h(sc2), h(s["scale"]))
