@@ -89,6 +89,11 @@ typedef struct mmpc_config {
                           j < L-1):  -max(c_{k,i,0..j}, c_{k-1,i,j+1..L-1}) <= s_k  (the entries j' > j still hold the PREVIOUS
                           stage's expressions; at k = 0 they hold free variables that can always satisfy the row).  These rows
                           tie x_k to x_{k-1}; the generic kernel carries them.  0: intended rows only */
+    int specialise;    /* 0 (the default): the handle runs what it ran before shape libraries existed - the built-in specialised
+                          kernels for the four listed shapes, the generic kernel otherwise.  1: when a shape library with the
+                          handle's (kind, N, M) has been loaded (mmpc_load_shape_library) before mmpc_create, the handle takes its
+                          kernels exactly as it takes a listed shape's; without one it runs the generic kernel.  Ignored for a listed
+                          shape, with half-space planes (L > 0) and for the pose-reference kind */
 } mmpc_config;
 
 typedef struct mmpc_handle_s *mmpc_handle;
@@ -261,6 +266,30 @@ int mmpc_lds_bytes(mmpc_handle h);
 /* problem instances (workgroups) the runtime keeps resident per compute unit for the kernel this handle launches
  * (hipOccupancyMaxActiveBlocksPerMultiprocessor: registers allow 4 - one wave per SIMD -, LDS may allow fewer) */
 int mmpc_problems_per_cu(mmpc_handle h);
+/* 1 when the handle's next launch runs a specialised kernel, 0 when it runs the generic one.  Decided per launch: dense weights
+ * (mmpc_set_weights) and the terminal equality (mmpc_set_terminal_xy_equality) move a handle that has specialised kernels to the
+ * generic one and back. */
+int mmpc_runs_specialised(mmpc_handle h);
+
+/* Shape libraries: specialised kernels for a (kind, N, M) outside the four built-in shapes, built on demand (build.py:
+ * build_shape_library compiles csrc/mmpc_shape.hip for one shape into csrc/shapes/libmmpc_shape_<kind>_<N>_<M>.so, one to two
+ * minutes of hipcc) and loaded into the running process.
+ * mmpc_shape_supported: 1 when (kind, N, M) lies inside the envelope of the specialised template, 0 otherwise - kinds 0 and 1;
+ * whole-body N in 1..20 or 23..31, base N in 1..55 (the number of box slacks a lane multiplies);
+ * whole-body M <= 11 up to N = 20 and M <= 16 beyond, base M <= 16 up to N = 31 and M <= 15 beyond; at most 64 KiB of LDS per
+ * problem in every obstacle mode.  THE GAP: whole-body N = 21 and 22 have no specialised kernel (the gain ring that the horizons
+ * from 21 on keep in LDS during the roll-out does not fit there) - such a config runs the generic kernel, with or without
+ * cfg.specialise.  The answer is arithmetic on the template's own bounds; of the shapes it admits, the test suite compiles and
+ * runs both upper edges of N, (0, 31, 8) and (1, 55, 1), on the GPU.
+ * mmpc_load_shape_library: opens the file at `path` and registers its six kernels ([one launch, budgeted / continuation] x
+ * obs_per_stage 0, 1, 2) for the process; handles created AFTERWARDS with cfg.specialise = 1 and that shape run them, budgets,
+ * continuations, list launches, the obstacle clock and the objective scaling included.  Handles created earlier keep their
+ * kernels; a library is never unloaded; loading a shape that is already there is a no-op that returns MMPC_OK.  MMPC_E_ARG when
+ * the file cannot be opened, is not a shape library, was built from other kernel sources than this library (the kernels'
+ * parameter block and argument list are no stable ABI: build.py hands both builds a tag of the sources' contents), or holds a
+ * shape outside the envelope; the text comes through mmpc_last_error with a NULL handle.  No GPU is needed to load.  Thread-safe. */
+int mmpc_shape_supported(int kind, int N, int M);
+int mmpc_load_shape_library(const char *path);
 const char *mmpc_last_error(mmpc_handle h);
 const char *mmpc_version(void);
 

@@ -22,7 +22,7 @@ from . import synth
 from . import interface_wholebody_qref
 from .interface_wholebody_qref import BatchedRecedingHorizon, Interface
 from .fleet import DeviceFleet
-from .build import build_extension
+from .build import build_extension, build_shape_library
 
 __all__ = ["Obstacles", "Base", "ManipulatorPanda3DoF", "MobileManipulator", "MPCWholeBody", "MPCBase", "MPCWholeBodyPoseRef",
-           "build_extension", "_capi", "BatchedRecedingHorizon", "Interface", "interface_wholebody_qref", "DeviceFleet", "synth"]
+           "build_extension", "build_shape_library", "_capi", "BatchedRecedingHorizon", "Interface", "interface_wholebody_qref", "DeviceFleet", "synth"]

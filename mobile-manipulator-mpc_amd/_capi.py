@@ -18,13 +18,15 @@ class MmpcConfig(C.Structure):
                 ("max_batch", C.c_int), ("device", C.c_int), ("max_iter", C.c_int),
                 ("dt", C.c_double), ("tol", C.c_double), ("mu_init", C.c_double),
                 ("ulim", (C.c_double * 5) * 2), ("xlim", (C.c_double * 9) * 2), ("dulim", (C.c_double * 5) * 2),
-                ("L", C.c_int), ("halfspace", (C.c_double * 6) * 8), ("as_written", C.c_int)]
+                ("L", C.c_int), ("halfspace", (C.c_double * 6) * 8), ("as_written", C.c_int), ("specialise", C.c_int)]
 
 
 EXPORTS = ["mmpc_create", "mmpc_destroy", "mmpc_set_weights", "mmpc_set_terminal_xy_equality", "mmpc_reset",
            "mmpc_solve_batch", "mmpc_solve_batch_device", "mmpc_get_u_latest", "mmpc_set_u_latest",
            "mmpc_lds_bytes", "mmpc_problems_per_cu", "mmpc_set_warm_start", "mmpc_set_schedule_hint", "mmpc_set_iteration_budget", "mmpc_resume_batch_device", "mmpc_solve_list_device", "mmpc_suspended_count", "mmpc_last_error", "mmpc_version", "mmpc_ik_batch", "mmpc_ik_batch_device",
-           "mmpc_tick_prepare_device", "mmpc_set_obstacle_clock", "mmpc_set_objective_scaling"]
+           "mmpc_tick_prepare_device", "mmpc_set_obstacle_clock", "mmpc_set_objective_scaling",
+           "mmpc_shape_supported", "mmpc_load_shape_library", "mmpc_runs_specialised"]
+LISTED_SHAPES = ((KIND_WHOLEBODY, 20, 5), (KIND_WHOLEBODY, 30, 8), (KIND_WHOLEBODY, 20, 3), (KIND_BASE, 15, 3))   # MMPC_FAST_LIST
 
 _lib = None
 _dp = C.POINTER(C.c_double)
@@ -72,6 +74,9 @@ def lib():
         L.mmpc_tick_prepare_device.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 8 + [C.c_void_p]
         L.mmpc_set_obstacle_clock.argtypes = [C.c_void_p, C.c_void_p]
         L.mmpc_set_objective_scaling.argtypes = [C.c_void_p, C.c_double, C.c_void_p]
+        L.mmpc_shape_supported.argtypes = [C.c_int, C.c_int, C.c_int]
+        L.mmpc_load_shape_library.argtypes = [C.c_char_p]
+        L.mmpc_runs_specialised.argtypes = [C.c_void_p]
         _lib = L
     return _lib
 
@@ -99,11 +104,61 @@ def ik_batch(q0, target_xz, device=0):
     return dict(q=q, status=st, iters=it)
 
 
+def prepare_shape(kind, N, M, specialise, planes=0):
+    """The `specialise` keyword of Engine, the controllers and DeviceFleet, before the handle is created.  Returns the value of
+    mmpc_config.specialise (1: a library with the shape's kernels is loaded in this process, 0: the handle runs what it runs
+    without the keyword).
+      False     nothing is looked up;
+      "cached"  the shape's library csrc/shapes/libmmpc_shape_<kind>_<N>_<M>.so is loaded when it exists and is current (no
+                older than the kernel sources, built from them), else the handle runs the generic kernel;
+      True      the library is built when it is missing or stale - ONE TO TWO MINUTES of hipcc, once per shape and source
+                version - and loaded.  ValueError for a shape outside the specialised envelope (mmpc_shape_supported), with
+                half-space planes and for the pose-reference kind.
+    A listed shape (LISTED_SHAPES) ignores the argument: it always runs its built-in kernels.  Dense weights and the terminal
+    equality fall back to the generic kernel per launch, as they do on a listed shape (Engine.runs_specialised).  A shape
+    library is not always the faster kernel: DESIGN.md section 4 has the measured table per shape."""
+    if specialise is False or specialise is None:
+        return 0
+    if specialise is not True and specialise != "cached":
+        raise ValueError("specialise must be False, True or 'cached' (got %r)" % (specialise,))
+    kind, N, M = int(kind), int(N), int(M)
+    if (kind, N, M) in LISTED_SHAPES:
+        return 0
+    from . import build
+    why = None
+    if kind == KIND_WHOLEBODY_POSE:
+        why = "the pose-reference kind has no specialised kernel"
+    elif planes:
+        why = "half-space planes run on the generic kernel only"
+    elif not build.shape_supported(kind, N, M):
+        why = "(kind, N, M) = (%d, %d, %d) is outside the envelope of the specialised kernels (mmpc_shape_supported)" % (kind, N, M)
+    if why:
+        if specialise is True:
+            raise ValueError("specialise=True: " + why)
+        return 0
+    if specialise is True:
+        path = build.build_shape_library(kind, N, M)
+        try:
+            build.load_shape_library(path)
+        except RuntimeError:      # (as new as the sources, yet not built from them: a copied file)
+            build.load_shape_library(build.build_shape_library(kind, N, M, force=True))
+        return 1
+    if not build.shape_library_current(kind, N, M):
+        return 0
+    try:
+        build.load_shape_library(build.shape_library_path(kind, N, M))
+    except RuntimeError:
+        return 0
+    return 1
+
+
 class Engine:
     """Owns one mmpc_handle (one controller's NLP structure on one GPU)."""
 
     def __init__(self, kind, N, M, dt, ulim, xlim, dulim, max_batch=1, device=0, obs_per_stage=False,
-                 tol=1e-8, mu_init=1.0, max_iter=2000, halfspaces=None, as_written=False):
+                 tol=1e-8, mu_init=1.0, max_iter=2000, halfspaces=None, as_written=False, specialise=False):
+        """specialise: False (default), "cached" or True - run the specialised kernels of a shape library for an unlisted
+        (kind, N, M); see prepare_shape (True may compile for one to two minutes)."""
         self.kind, self.N, self.M = kind, int(N), int(M)
         self.nx, self.nu = (6, 2) if kind == KIND_BASE else (9, 5)
         self.nref = 4 if kind == KIND_WHOLEBODY_POSE else self.nx      # reference row: endpoint pose (x,y,z,psi) or the state
@@ -125,6 +180,7 @@ class Engine:
                 cfg.xlim[r][j] = xlim[r, j] if j < self.nx else 0.0
         cfg.L = 0
         cfg.as_written = int(bool(as_written))
+        cfg.specialise = prepare_shape(kind, N, M, specialise, planes=0 if halfspaces is None else len(halfspaces))
         if halfspaces is not None and len(halfspaces):
             hs = np.asarray(halfspaces, float).reshape(-1, 6)
             if hs.shape[0] > 8:
@@ -160,6 +216,11 @@ class Engine:
     @property
     def lds_bytes(self):
         return lib().mmpc_lds_bytes(self._h)
+
+    @property
+    def runs_specialised(self):
+        """mmpc_runs_specialised: the next launch runs a specialised kernel (follows the weights and the terminal equality)"""
+        return bool(lib().mmpc_runs_specialised(self._h))
 
     @property
     def problems_per_cu(self):

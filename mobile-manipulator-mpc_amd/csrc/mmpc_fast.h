@@ -149,8 +149,8 @@ struct MmpcFastDims {
     // division by 14 and the addresses derived from it, ~25 instructions per pass in each of the four pair-lane phases of an
     // iteration).  Padded map (where it needs no extra pass): a 16-lane row of the wave owns one stage per pass, row 4 p + (l >> 4),
     // column l & 15 < NV is the variable; the pairs of the terminal stage (states only) sit in column NV of the first NX rows.  Every
-    // address is then base(l) + p * stride(l), both formed once per phase.
-    static constexpr bool PADMAP = MMPC_PADMAP && NV < 16 && NX <= N && (N * 16 + MMPC_WAVE - 1) / MMPC_WAVE <= (NPAIR + MMPC_WAVE - 1) / MMPC_WAVE;
+    // address is then base(l) + p * stride(l), both formed once per phase.  (Not written for the slim layout: the long horizons take the plain map.)
+    static constexpr bool PADMAP = MMPC_PADMAP && N < MMPC_SLIM_NMIN && NV < 16 && NX <= N && (N * 16 + MMPC_WAVE - 1) / MMPC_WAVE <= (NPAIR + MMPC_WAVE - 1) / MMPC_WAVE;
     // stride of the per-stage trig cache (8 words used): with 8 the stage lanes' words sit 16 dwords apart - two LDS banks for 21 lanes;
     // the long horizons have no LDS to spare for the padding
     static constexpr int TRGS = N >= MMPC_SLIM_NMIN ? 8 : 9;
@@ -170,7 +170,8 @@ struct MmpcFastDims {
     // in the stage lane, where their arithmetic fills the latency of the trigonometry around it (measured: -0.9 % at N = 20
     // when split, +11 % at N = 30, +2.6 % for the base kind).
     static constexpr int RG = ((N >= MMPC_RG_NMIN || KIND == 1) && 2 * NS <= MMPC_WAVE) ? (MMPC_WAVE / NS < MMPC_RG_MAX ? MMPC_WAVE / NS : MMPC_RG_MAX) : 1;
-    static_assert(NV + 1 <= 16, "stage matrix over (x, 1, u) must fit one 16x16 tile");
+    static constexpr bool TILE_OK = NV + 1 <= 16;
+    static_assert(TILE_OK, "stage matrix over (x, 1, u) must fit one 16x16 tile");
 };
 
 
@@ -247,6 +248,62 @@ MMPC_HD int mmpc_fast_state_doubles(int MC) {
     return F::NPAIR + F::NS + F::NS * F::NX + 2 * MMPC_FCAP + MMPC_NSCAL + MMPC_WAVE * (2 * F::NPASS + 2 * (MC > 0 ? MC : 1) + 8);
 }
 
+// The envelope of the specialised template, in one place: every bound mmpc_solve_fast asserts statically (mmpc_fast.h,
+// mmpc_fast_iter.inc) is a member here, the assertions read these members, and mmpc_fast_shape_ok (below) is their conjunction -
+// what mmpc_shape_supported answers and what a shape library (mmpc_shape.hip) is refused by.
+template <int KIND, int N>
+struct MmpcFastEnvelope {
+    typedef MmpcFastDims<KIND, N> F;
+    typedef MmpcGainBlock<KIND, N> GB;
+    static constexpr bool SLIM = N >= MMPC_SLIM_NMIN;
+    // stages per trip of the Riccati / forward loops: unrolling saves the per-stage pointer bumps and register shuffles,
+    // but costs registers - it only pays where the kernel does not spill (measured per instantiation)
+    static constexpr bool ROOMY = KIND == 0 && N <= MMPC_UNROLL_NMAX;
+    // (gains in global memory, MmpcGainBlock: the gain ring of the roll-out rotates its registers statically, so the roll-out of
+    //  those horizons is fully unrolled whether the instantiation is roomy or not)
+    static constexpr int RIC_UNROLL = ROOMY ? MMPC_RIC_UNROLL : 1, FWD_UNROLL = (ROOMY || GB::ON) ? (MMPC_FWD_UNROLL < N ? MMPC_FWD_UNROLL : N) : 1;
+    static constexpr int GRS = F::NU * F::NX + F::NU;   // elements of a stage's (K_k, kf_k): a slot of the gain ring
+    static constexpr bool RING_FITS = !GB::ON || 4 * GRS <= F::NU * F::NX + F::NUU + F::NS + F::NS * F::NU;
+    static constexpr bool RING_UNROLLED = !GB::ON || FWD_UNROLL >= N;
+    static constexpr bool SLIM_MAP_OK = !(SLIM && F::PADMAP);
+    static constexpr bool Q1_ITEMS_OK = F::NXX + F::NU * F::NX + F::NUU + F::NV <= 2 * MMPC_WAVE && F::NV + 2 <= 32;
+    static constexpr bool ROLL_ROW_OK = F::NX <= 16;   // the roll-out's row lanes share a row of 16 lanes
+    // scratch of the second-order correction (io.soc, sized by mmpc_soc_doubles): direction | residuals of the trial point | running c_soc
+    static constexpr int nrs(int MC) { return (MC > 0 ? MC : 0) + F::NSELF; }   // rows per stage that are not box rows
+    static constexpr int soc_used(int MC) { return (F::NS * F::NV + F::NS + F::NS * F::NX) + F::NS * F::NX + F::NS * nrs(MC) + F::NS * F::NX + F::NS * nrs(MC); }
+    static constexpr bool soc_ok(int MC) { return soc_used(MC) <= mmpc_soc_doubles(N, F::NX, F::NU, nrs(MC)); }
+    static constexpr int mcr(int MC) { return MC > 0 ? (MC + F::RG - 1) / F::RG : 1; }   // circle rows per lane
+    // MmpcLogAcc: the largest number of factors one lane multiplies between init() and value() (see MmpcLogAcc)
+    static constexpr int LOGF_BOX = 2 * F::NPASS;
+    static constexpr int logf_row(int MC) { return (F::RG > 1 ? mcr(MC) : MC) + F::NSELF; }
+    static constexpr int logf(int MC) { return LOGF_BOX > logf_row(MC) ? LOGF_BOX : logf_row(MC); }
+    static constexpr bool log_high_ok(int MC) { return 19 * logf(MC) < 300; }
+    static constexpr bool LOG_LOW_OK = 15 * LOGF_BOX < 300;
+    // the static LDS block of a workgroup: 64 KiB at most, in every obstacle mode
+    static constexpr bool lds_ok(int MC) {
+        for (int ops = 0; ops < 3; ops++) if (mmpc_fast_layout<KIND, N>(MC, ops).total * (int)sizeof(double) > 64 * 1024) return false;
+        return true;
+    }
+    static constexpr bool ok(int MC) {
+        return MC >= 0 && F::TILE_OK && SLIM_MAP_OK && Q1_ITEMS_OK && ROLL_ROW_OK && RING_FITS && RING_UNROLLED && LOG_LOW_OK && log_high_ok(MC) &&
+               soc_ok(MC) && lds_ok(MC);
+    }
+};
+// mmpc_fast_shape_ok(kind, N, M): mmpc_solve_fast<kind, N, M> is inside the template's envelope (whole-body with a joint reference
+// and base kind; N, M in the ranges mmpc_create takes).  N is a template parameter of every bound, so the run-time N is looked up.
+#define MMPC_SHAPE_NMAX 63
+#define MMPC_SHAPE_MMAX 16
+template <int KIND, int N = MMPC_SHAPE_NMAX>
+struct MmpcEnvelopeScan {
+    static constexpr bool ok(int n, int MC) { return n == N ? MmpcFastEnvelope<KIND, N>::ok(MC) : MmpcEnvelopeScan<KIND, N - 1>::ok(n, MC); }
+};
+template <int KIND>
+struct MmpcEnvelopeScan<KIND, 0> { static constexpr bool ok(int, int) { return false; } };
+MMPC_HD constexpr bool mmpc_fast_shape_ok(int kind, int N, int M) {
+    if (N < 1 || N > MMPC_SHAPE_NMAX || M < 0 || M > MMPC_SHAPE_MMAX) return false;
+    return kind == 0 ? MmpcEnvelopeScan<0>::ok(N, M) : (kind == 1 ? MmpcEnvelopeScan<1>::ok(N, M) : false);
+}
+
 template <int KIND, int N, int MC>
 struct MmpcLaneState {
     typedef MmpcFastDims<KIND, N> F;
@@ -257,7 +314,7 @@ struct MmpcLaneState {
     // the bounds themselves (constant during a solve: the merged input box uses U_last); -+1e300 marks an absent side
     double b_lo[F::NPASS], b_hi[F::NPASS];
     // circle rows m = s + RG r of stage k, lane = s NS + k  (RG = 1: the rows of stage `lane`)
-    static constexpr int MCR = MC > 0 ? (MC + F::RG - 1) / F::RG : 1;   // circle rows per lane
+    static constexpr int MCR = MmpcFastEnvelope<KIND, N>::mcr(MC);   // circle rows per lane
     double ct[MCR], cz[MCR], cdt[MCR];
     double cp[F::RG > 1 ? 9 : 1];                    // RG > 1: partial sums of this lane's circle rows, from a row phase to the stage phase after it
     // self-collision rows of stage `lane`
@@ -390,16 +447,16 @@ MMPC_DEV void mmpc_solve_fast(const MmpcParams &P, const MmpcIO io, double *lds 
     // MmpcLogAcc multiplies its factors without rescaling: the largest number of factors one lane multiplies between init() and value()
     // in this instantiation (E1 of mmpc_fast_iter.inc: row lanes + stage lanes form one chain, the pair lanes another) must keep
     // the product inside the normal range - box slacks lie in [1e-15, 2e19], a row slack is a distance: below 1e19 like every bound
-    constexpr int LOGF_BOX = 2 * NPASS, LOGF_ROW = (RG > 1 ? MCR : M) + NSELF, LOGF = LOGF_BOX > LOGF_ROW ? LOGF_BOX : LOGF_ROW;
-    static_assert(19 * LOGF < 300, "MmpcLogAcc: the product of this many slacks of 1e19 can overflow");
-    static_assert(15 * LOGF_BOX < 300, "MmpcLogAcc: the product of this many box slacks of 1e-15 can leave the normal range");
+    typedef MmpcFastEnvelope<KIND, N> ENV;
+    static_assert(ENV::log_high_ok(MC), "MmpcLogAcc: the product of this many slacks of 1e19 can overflow");
+    static_assert(ENV::LOG_LOW_OK, "MmpcLogAcc: the product of this many box slacks of 1e-15 can leave the normal range");
+    static_assert(KIND == 0 || KIND == 1, "the specialised template carries the joint-reference whole-body kind and the base kind");
+    static_assert(mmpc_fast_shape_ok(KIND, N, MC), "(kind, N, M) is outside the specialised template's envelope (MmpcFastEnvelope)");
 // lane -> (row group rs, stage rk) of the circle rows; row slot r of the lane is obstacle rs + RG r
 #define MMPC_ROW_LANE const int rs = RG > 1 ? lane / NS : 0, rk = lane - rs * NS; const bool rlane = M > 0 && lane < RG * NS;
-    // stages per trip of the Riccati / forward loops: unrolling saves the per-stage pointer bumps and register shuffles,
-    // but costs registers - it only pays where the kernel does not spill (measured per instantiation)
-    constexpr bool ROOMY = KIND == 0 && N <= MMPC_UNROLL_NMAX;
+    // stages per trip of the Riccati / forward loops (MmpcFastEnvelope)
     constexpr bool SLIM = N >= MMPC_SLIM_NMIN;   // references and per-stage obstacles are read from HBM/L2 (see mmpc_fast_layout)
-    constexpr int RIC_UNROLL = ROOMY ? MMPC_RIC_UNROLL : 1, FWD_UNROLL = ROOMY ? (MMPC_FWD_UNROLL < N ? MMPC_FWD_UNROLL : N) : 1;
+    constexpr int RIC_UNROLL = ENV::RIC_UNROLL, FWD_UNROLL = ENV::FWD_UNROLL;
     const MmpcFastLayout L = mmpc_fast_layout<KIND, N>(M, ops);
     double *XU = lds + L.XU, *S = lds + L.S, *LAM = lds + L.LAM, *XUREF = lds + L.XUREF, *ULAST = lds + L.ULAST,
            *OBS = lds + L.OBS, *CST = lds + L.CST, *CV = lds + L.CV, *CD = lds + L.CD, *TRG = lds + L.TRG, *HXX = lds + L.HXX,
@@ -574,7 +631,7 @@ MMPC_DEV void mmpc_solve_fast(const MmpcParams &P, const MmpcIO io, double *lds 
             // items e = lane + 64 t of the dense blocks the elimination of s_{N-1} adds to stage N-1 (see the backward pass):
             // Hxx -= a a^T / h (packed lower triangle), Hux = -b a^T / h, Huu = -b b^T / h, q += (a; b) gamma / h with (a; b) = Q1V[0 .. NV),
             // gamma / h = Q1V[NV]; slots without an item multiply two zeros of the constant block into the lane's dump slot
-            static_assert(NXX + NU * NX + NUU + NV <= 2 * MMPC_WAVE && NV + 2 <= 32, "stage-(N-1) block items: two per lane");
+            static_assert(ENV::Q1_ITEMS_OK, "stage-(N-1) block items: two per lane");
 #pragma unroll
             for (int t = 0; t < 2; t++) {
                 const int e = lane + MMPC_WAVE * t;
@@ -874,7 +931,7 @@ MMPC_DEV void mmpc_solve_fast(const MmpcParams &P, const MmpcIO io, double *lds 
     constexpr int NRS = (MC > 0 ? MC : 0) + NSELF;                                     // rows per stage that are not box rows
     constexpr int O_D = 0, O_TC = O_D + NS * NV + NS + NS * NX, O_TR = O_TC + NS * NX,  // direction | residuals of the trial point
                   O_AC = O_TR + NS * NRS, O_AR = O_AC + NS * NX;                         // running c_soc (dynamics | rows)
-    static_assert(O_AR + NS * NRS <= mmpc_soc_doubles(N, NX, NU, NRS), "second-order correction scratch");
+    static_assert(O_AR + NS * NRS == ENV::soc_used(MC) && ENV::soc_ok(MC), "second-order correction scratch");
     int soc_st = 0, soc_p = 0, fatal = 0;
     double a_soc = 0.0, alpha0 = 0.0, a_prev = 0.0, th_prev = 0.0;
 #ifdef MMPC_EMU

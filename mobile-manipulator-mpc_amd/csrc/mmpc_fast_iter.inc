@@ -164,7 +164,7 @@
         // long horizons read the references and the previous inputs from HBM / L2: the loads of ALL passes ahead of the loop (one
         // exposed round trip instead of one per pass)
         double g_ref[SLIM ? NPASS : 1], g_ul[SLIM ? NPASS : 1];
-        static_assert(!(SLIM && F::PADMAP), "the padded pair map is not written for the slim layout");
+        static_assert(ENV::SLIM_MAP_OK, "the padded pair map is not written for the slim layout");
         if (SLIM) {
 #pragma unroll
             for (int p = 0; p < NPASS; p++) {
@@ -690,9 +690,9 @@
             // LDS - over the stage-matrix extras HUXL .. HUUD, dead since the backward pass - is filled two stages ahead of the
             // chain from registers that were loaded from the gain block three stages before that; the row lanes read their gain
             // row from the ring one stage ahead, as they read it from the LDS copy of the short horizons.
-            constexpr int GRS = NU * NX + NU;
-            static_assert(!GK || 4 * GRS <= NU * NX + NUU + NS + NS * NU, "the gain ring must fit the stage-matrix extras");
-            static_assert(!GK || FWD_UNROLL >= N, "the gain ring's registers rotate statically: the roll-out must be fully unrolled");
+            constexpr int GRS = ENV::GRS;
+            static_assert(ENV::RING_FITS, "the gain ring must fit the stage-matrix extras");
+            static_assert(ENV::RING_UNROLLED, "the gain ring's registers rotate statically: the roll-out must be fully unrolled");
             double *const RING = lds + L.HUXL;
             double gpre[3] = {0.0, 0.0, 0.0};
             unsigned g_off = 0, g_st = 0;
@@ -767,7 +767,7 @@
 #ifndef MMPC_EMU
                 // (the rows of the dynamics sit in lanes 0 .. NX-1, all in the first row of 16 lanes: dx_k[j] by a row broadcast; the
                 //  other rows of the wave broadcast their own lanes' don't-care values and store to their dump slots)
-                static_assert(NX <= 16, "the roll-out's row lanes must share a row of 16 lanes");
+                static_assert(ENV::ROLL_ROW_OK, "the roll-out's row lanes must share a row of 16 lanes");
                 mmpc_rowbcast_all<0, NX>(ls.fw[MMPC_FW_SLOT(k)], dx);
 #else
 #pragma unroll

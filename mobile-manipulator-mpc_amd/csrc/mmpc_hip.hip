@@ -2,17 +2,22 @@
 // One 64-lane workgroup (= one wavefront) per problem instance; the solver core is
 // mmpc_core.h.  No CPU fallback: every entry point needs a HIP device.
 // From a config to a kernel: mmpc_create resolves the handle's kernels once (resolve_kernels: the generic one, and the specialised
-// pair when MMPC_FAST_LIST has the shape) and keeps them as typed pointers; launch() picks by runs_fast() and launches through them.
+// pair when MMPC_FAST_LIST has the shape, or - for a handle created with cfg.specialise - when a shape library with it has been
+// loaded, mmpc_load_shape_library) and keeps them as typed pointers; launch() picks by runs_fast() and launches through them.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <dlfcn.h>
+#include <mutex>
 #include <new>
+#include <vector>
 
 #include "../../include/mmpc.h"
 #include "mmpc_core.h"
 #include "mmpc_fast.h"
+#include "mmpc_fast_kernel.h"
 #include "mmpc_ik.h"
 #include "mmpc_tick.h"
 
@@ -72,50 +77,6 @@ __global__ __launch_bounds__(MMPC_WAVE) void mmpc_solve_kernel_static(
 #ifndef MMPC_STATIC_LIST   // (experiments build shorter lists: tools/build_variant.sh)
 #define MMPC_STATIC_LIST(X) X(0, 20, 3, 0, 2, 1) X(0, 20, 3, 0, 2, 0) X(0, 20, 3, 0, 3, 1) X(0, 20, 3, 0, 0, 0) X(0, 20, 5, 0, 0, 0)
 #endif
-
-// OPS = the config's obs_per_stage (0 static record, 1 table per stage, 2 motion record + clock): part of the LDS layout.  The LDS block is STATIC (its size is a
-// constant of the instantiation): with `extern __shared__` the base of the dynamic block is resolved after instruction
-// selection and every lane-derived LDS address carries an add of that constant 0 (14 of the ~200 instructions of a Riccati stage).
-template <int KIND, int N, int MC, int WPE, bool CONT, int OPS>
-__global__ __launch_bounds__(MMPC_WAVE, WPE) void mmpc_fast_kernel(
-    const MmpcParams *__restrict__ Pp, int B, const double *__restrict__ x_init, const double *__restrict__ traj_ref,
-    const double *__restrict__ u_ref, const double *__restrict__ u_last, const double *__restrict__ x_guess,
-    const double *__restrict__ obs, double *__restrict__ X, double *__restrict__ U, double *__restrict__ s,
-    int *__restrict__ status, int *__restrict__ iters, double *__restrict__ cost, double *__restrict__ err,
-    const int *__restrict__ order, int budget, double *__restrict__ state, int state_stride, const int *__restrict__ resume_count,
-    const int *__restrict__ list_count, double *__restrict__ gscr, double *__restrict__ soc, int soc_stride,
-    const long long *__restrict__ tick, double scale_max_grad, double *__restrict__ scale_out) {
-    __shared__ double lds[mmpc_fast_layout<KIND, N>(MC, OPS).total];
-    // A continuation launch (resume_count != null): `order` is the compacted list of the suspended instances, *resume_count its
-    // length, and the grid is SMALL (MMPC_RESUME_GRID workgroups that stride over the list): a handful of instances is left,
-    // and a grid of B workgroups that almost all exit at once would still have to be dispatched one by one - in a stream of
-    // batches that competes with the next batch's launch.
-    // A list launch (list_count != null, mmpc_solve_list_device): `order` is the caller's list of instances, *list_count its length
-    // (read on the device: the caller need not know it), the grid is the list's capacity.
-    const int limit = resume_count ? *resume_count : (list_count ? *list_count : B);
-    for (int w = (int)blockIdx.x; w < limit; w += (int)gridDim.x) {
-        // launch order: workgroup i solves instance order[i] (a permutation / a list; results do not depend on it)
-        const int b = order ? order[w] : w;
-        // (a list launch takes its row indices from the caller's device memory, where nothing can have checked them: an index
-        //  outside the batch is skipped - it would address the inputs, the outputs and the handle's own save areas)
-        if ((unsigned)b >= (unsigned)B) { if (!CONT || !resume_count) break; continue; }
-        const MmpcParams &P = *Pp;
-        const int M = MC;
-        const size_t so = OPS == 2 ? (size_t)M * 5 : (size_t)(P.obs_per_stage ? N + 1 : 1) * M * 3;
-        MmpcIO io;
-        mmpc_instance_io<KIND>(io, P, b, N, so, x_init, traj_ref, u_ref, u_last, x_guess, obs, X, U, s, status, iters, cost, err,
-                               soc, soc_stride);
-        io.state = state ? state + (size_t)b * state_stride : nullptr;
-        io.budget = budget;
-        io.resume = resume_count ? 1 : 0;
-        io.gscr = MmpcGainBlock<KIND, N>::ON ? gscr + (size_t)b * MmpcGainBlock<KIND, N>::total : nullptr;
-        if (OPS == 2 && tick) io.tick = tick + b;   // the clock is indexed by instance row, like every per-instance array
-        io.scale_max_grad = scale_max_grad; if (scale_out) io.scale_out = scale_out + b;   // (objective scaling; by instance row too)
-        mmpc_solve_fast<KIND, N, MC, CONT, OPS>(P, io, lds);
-        if (!CONT || !resume_count) break;      // (one instance per workgroup except in a continuation launch)
-        __builtin_amdgcn_s_barrier();           // the next instance reuses the LDS block
-    }
-}
 
 // (kind, N, M) triples with a specialised kernel; everything else runs the generic kernel.
 // BASELINE configs C3/C4 (0,20,5), C5 (0,30,8), C2 (1,15,3); the reference demo (0,20,3).
@@ -263,13 +224,10 @@ __global__ void mmpc_cold_xguess(int B, int NS, int NX, int clip, const MmpcPara
     }
 }
 
-// the signature of mmpc_solve_kernel<> and mmpc_solve_kernel_static<>, and that of mmpc_fast_kernel<>
+// the signature of mmpc_solve_kernel<> and mmpc_solve_kernel_static<> (that of mmpc_fast_kernel<>: mmpc_fast_fn, mmpc_fast_kernel.h)
 typedef void (*mmpc_gen_fn)(const MmpcParams *, int, const double *, const double *, const double *, const double *, const double *,
                             const double *, double *, double *, double *, int *, int *, double *, double *, const int *, double *, int,
                             const long long *, double, double *);
-typedef void (*mmpc_fast_fn)(const MmpcParams *, int, const double *, const double *, const double *, const double *, const double *,
-                             const double *, double *, double *, double *, int *, int *, double *, double *, const int *, int, double *,
-                             int, const int *, const int *, double *, double *, int, const long long *, double, double *);
 
 struct mmpc_handle_s {
     mmpc_config cfg;
@@ -392,8 +350,76 @@ static thread_local char g_err[512] = "";   // errors of the handle-less entry p
 extern "C" const char *mmpc_last_error(mmpc_handle h) { return h ? h->err : g_err; }
 // this launch uses the specialised kernel (decided per call: weights and the terminal equality change after create)
 static bool runs_fast(mmpc_handle h) { return h->fast_fn[0] && h->diag && !h->hp.terminal_xy_eq && !h->force_generic_env; }
+extern "C" int mmpc_runs_specialised(mmpc_handle h) { return h ? (runs_fast(h) ? 1 : 0) : MMPC_E_ARG; }
 extern "C" int mmpc_problems_per_cu(mmpc_handle h) { return h ? (runs_fast(h) ? h->fast_per_cu : h->per_cu) : MMPC_E_ARG; }
 extern "C" int mmpc_lds_bytes(mmpc_handle h) { return h ? (runs_fast(h) ? h->fast_lds_bytes : h->lds_bytes) : MMPC_E_ARG; }
+
+// ---- shape libraries (mmpc_shape.hip): the specialised kernels of one (kind, N, M) each, loaded into the process on request.
+// The registry is process-wide, filled under a mutex, and only grows: a library is never unloaded (handles keep pointers into it).
+static std::mutex g_shape_mutex;
+static std::vector<MmpcShapeDesc> &shape_registry() { static std::vector<MmpcShapeDesc> r; return r; }
+static bool find_shape(int kind, int N, int M, MmpcShapeDesc *out) {
+    std::lock_guard<std::mutex> lock(g_shape_mutex);
+    for (const MmpcShapeDesc &d : shape_registry())
+        if (d.kind == kind && d.N == N && d.M == M) { *out = d; return true; }
+    return false;
+}
+static bool listed_shape(int kind, int N, int M) {
+#define MMPC_X(K, NN, MM, WW) if (kind == K && N == NN && M == MM) return true;
+    MMPC_FAST_LIST(MMPC_X)
+#undef MMPC_X
+    return false;
+}
+
+extern "C" int mmpc_shape_supported(int kind, int N, int M) { return mmpc_fast_shape_ok(kind, N, M) ? 1 : 0; }
+
+extern "C" int mmpc_load_shape_library(const char *path) {
+    if (!path || !*path) { snprintf(g_err, sizeof(g_err), "mmpc_load_shape_library: no path"); return MMPC_E_ARG; }
+    // (a descriptor is read before anything of the library is trusted; a refused library stays mapped - its kernels are
+    //  registered with the HIP runtime at load time - but nothing points into it)
+    void *so = dlopen(path, RTLD_NOW | RTLD_LOCAL);
+    if (!so) { snprintf(g_err, sizeof(g_err), "mmpc_load_shape_library: cannot open %.200s: %.200s", path, dlerror()); return MMPC_E_ARG; }
+    typedef void (*describe_fn)(MmpcShapeDesc *, unsigned long long);
+    describe_fn describe = (describe_fn)dlsym(so, MMPC_SHAPE_ENTRY);
+    if (!describe) {
+        snprintf(g_err, sizeof(g_err), "mmpc_load_shape_library: %.300s is not a shape library (no symbol %s)", path, MMPC_SHAPE_ENTRY);
+        return MMPC_E_ARG;
+    }
+    // the head first (the part of the descriptor that is the same in every version of the sources), the whole descriptor only
+    // when the library's magic, tag and descriptor size are this library's own: nothing is written behind `d` by a refused library
+    MmpcShapeDesc d;
+    memset(&d, 0, sizeof(d));
+    describe(&d, sizeof(MmpcShapeHead));
+    if (d.head.magic != MMPC_SHAPE_MAGIC) {
+        snprintf(g_err, sizeof(g_err), "mmpc_load_shape_library: %.300s is not a shape library (bad descriptor)", path);
+        return MMPC_E_ARG;
+    }
+    if (d.head.source_tag != (unsigned long long)MMPC_SOURCE_TAG) {
+        snprintf(g_err, sizeof(g_err), "mmpc_load_shape_library: %.250s was built from other kernel sources (source tag %016llx, this library has %016llx): rebuild it",
+                 path, d.head.source_tag, (unsigned long long)MMPC_SOURCE_TAG);
+        return MMPC_E_ARG;
+    }
+    if (d.head.desc_bytes != sizeof(MmpcShapeDesc)) {
+        snprintf(g_err, sizeof(g_err), "mmpc_load_shape_library: %.300s is not a shape library (bad descriptor size)", path);
+        return MMPC_E_ARG;
+    }
+    describe(&d, sizeof(d));
+    if (!mmpc_fast_shape_ok(d.kind, d.N, d.M)) {
+        snprintf(g_err, sizeof(g_err), "mmpc_load_shape_library: %.250s holds shape (%d, %d, %d), outside the specialised envelope (mmpc_shape_supported)",
+                 path, d.kind, d.N, d.M);
+        return MMPC_E_ARG;
+    }
+    for (int o = 0; o < 3; o++) for (int c = 0; c < 2; c++) if (!d.fn[o][c]) {
+        snprintf(g_err, sizeof(g_err), "mmpc_load_shape_library: %.300s is not a shape library (a kernel is missing)", path);
+        return MMPC_E_ARG;
+    }
+    std::lock_guard<std::mutex> lock(g_shape_mutex);
+    for (const MmpcShapeDesc &e : shape_registry())
+        if (e.kind == d.kind && e.N == d.N && e.M == d.M) { g_err[0] = 0; return MMPC_OK; }   // the shape is there already: a no-op
+    shape_registry().push_back(d);
+    g_err[0] = 0;
+    return MMPC_OK;
+}
 
 // A config becomes its kernels here and nowhere else (cfg, hp and lds_bytes are set): each list is expanded once, the launches
 // go through the pointers.  The static-LDS generic instantiation of a listed shape replaces mmpc_solve_kernel<kind>.
@@ -429,6 +455,16 @@ static void resolve_kernels(mmpc_handle h) {
     }
     MMPC_FAST_LIST(MMPC_X)
 #undef MMPC_X
+    // ... then the loaded shape libraries, for a handle that asked (cfg.specialise): a listed shape always runs its built-in kernels
+    MmpcShapeDesc d;
+    if (!h->fast_fn[0] && c.specialise && c.L == 0 && c.kind != MMPC_KIND_WHOLEBODY_POSE && !listed_shape(c.kind, c.N, c.M) &&
+        find_shape(c.kind, c.N, c.M, &d)) {
+        h->fast_fn[0] = d.fn[p.obs_per_stage][0];
+        h->fast_fn[1] = d.fn[p.obs_per_stage][1];
+        h->state_doubles = d.state_doubles;
+        h->gscr_doubles = d.gscr_doubles;
+        h->fast_lds_bytes = d.lds_bytes[p.obs_per_stage];
+    }
 }
 
 extern "C" int mmpc_create(const mmpc_config *cfg, mmpc_handle *out) {
