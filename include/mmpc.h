@@ -44,6 +44,12 @@ extern "C" {
 #define MMPC_STATUS_SUSPENDED 3 /* iteration budget of the launch used up (mmpc_set_iteration_budget): X, U, s hold the current
                                    iterate, mmpc_resume_batch_device continues the solve */
 
+/* per-robot task phase of a fleet mission (mmpc_mission_prepare_device): the task_flag of interface_wholebody_qref.py:146-228 */
+#define MMPC_PHASE_MOVE 0     /* 'move': track the nearest window of the global plan */
+#define MMPC_PHASE_APPROACH 1 /* 'approach': inside the 2 m box around the goal - hold the goal pose, terminal-xy equality on */
+#define MMPC_PHASE_ROTATE 2   /* 'rotate': within 0.2 m of the goal - the same with the weights diag(5,5,5,0,0,1,1,1,1) */
+#define MMPC_PHASE_DONE 3     /* 'move finish': reached at 1 cm and 0.5 degrees; the robot is frozen */
+
 /* Build-time structure of the NLP = constructor arguments of MPCWholeBody.__init__
  * (mpc_wholebody_qref.py:7-23: N, ulim, xlim, dulim, robot.dt) / MPCBase.__init__
  * (mpc_base.py:7-17).  +-INFINITY marks an absent bound (the reference uses ca.inf). */
@@ -145,8 +151,19 @@ int mmpc_solve_batch_device(mmpc_handle h, int B, const double *d_x_init, const 
  * are expected to take longest first); the handle's schedule hint is not used and not updated.  With an iteration budget set the
  * listed instances that need more are suspended as in mmpc_solve_batch_device and mmpc_resume_batch_device (same B) continues
  * exactly them.  What it is for: a receding-horizon loop over many robots in which the robots whose solve is finished advance
- * to their next tick while the few suspended ones are still being continued on another stream (bench.py --config c5). */
+ * to their next tick while the few suspended ones are still being continued on another stream (bench.py --config c5).
+ * A handle that runs the generic kernel is refused (MMPC_E_UNSUPPORTED): mmpc_solve_rows_device is the list launch for either family. */
 int mmpc_solve_list_device(mmpc_handle h, int B, const int *d_list, const int *d_count, int capacity, const double *d_x_init,
+                           const double *d_traj_ref, const double *d_u_ref, const double *d_u_last, const double *d_x_guess,
+                           const double *d_obs, double *d_X, double *d_U, double *d_s, int *d_status, int *d_iters,
+                           double *d_cost, double *d_err, void *stream);
+
+/* List launch on whichever kernel the handle runs (no reference counterpart).  Semantics of mmpc_solve_list_device - listed rows
+ * only, entries outside [0, B) skipped, unlisted rows neither read nor written, the grid is `capacity` - on a specialised handle (there
+ * it IS that launch) and on a generic one: weights the specialised kernels refuse, the terminal-xy equality, an unlisted shape.  No
+ * iteration budget: MMPC_E_UNSUPPORTED when the handle has one set (continuations stay with mmpc_solve_list_device).  What it is
+ * for: the per-phase lists of mmpc_mission_prepare_device, whose 'approach' and 'rotate' handles carry the terminal equality. */
+int mmpc_solve_rows_device(mmpc_handle h, int B, const int *d_list, const int *d_count, int capacity, const double *d_x_init,
                            const double *d_traj_ref, const double *d_u_ref, const double *d_u_last, const double *d_x_guess,
                            const double *d_obs, double *d_X, double *d_U, double *d_s, int *d_status, int *d_iters,
                            double *d_cost, double *d_err, void *stream);
@@ -254,6 +271,30 @@ int mmpc_suspended_count(mmpc_handle h, int *count);
 int mmpc_tick_prepare_device(mmpc_handle h, int B, double *d_x, long long *d_tick, const double *d_U_prev, const double *d_glob,
                              int nglob, const double *d_obs0, const double *d_vel, double *d_x_in, double *d_traj_ref, int *d_start,
                              double *d_obs, double *d_u_guess, double *d_x_guess, void *stream);
+
+/* mmpc_tick_prepare_device with the reference's task state machine per robot (interface_wholebody_qref.py:146-197, up to 'move
+ * finish'; the manipulate phase is not covered).  Handle requirements, argument checks, stream ordering and "no allocation, copy or
+ * synchronisation" as there; in addition d_phase [B] (int32, MMPC_PHASE_*, in/out: the phase the robot was last solved in), d_glob,
+ * d_lists [3][B] and d_counts [4] (int32) are required, and one hipMemsetAsync of the four counts is queued before the kernel.  Per
+ * robot b, with g = glob[b][nglob - 1] (the goal) and p = d_phase[b]:
+ *   1. advance as in mmpc_tick_prepare_device, only when d_U_prev is given and p != DONE.  A DONE robot is frozen: its rows of x,
+ *      tick, x_in, traj_ref, start and obs are neither read for output nor written, and it appears in no list (a phase code outside
+ *      0..3 counts as DONE);
+ *   2. state machine on the unclipped state after the advance, in this order, several transitions per call possible:
+ *      p == MOVE and |x0 - g0| <= 2 and |x1 - g1| <= 2  =>  APPROACH;   p in {MOVE, APPROACH} and d <= 0.2  =>  ROTATE;
+ *      p == ROTATE and |angleDiff(x2, g2)| <= 0.5 pi / 180 and d <= 0.01  =>  DONE,  with d = sqrt(dx dx + dy dy) and angleDiff
+ *      the controllers' (fmod(a + pi, 2 pi) - pi of both arguments, then the sign cases).  A comparison with a NaN is false: a
+ *      non-finite robot keeps its phase and its NaN reaches the solve;
+ *   3. for p != DONE: d_x_in = clip(x); the obstacle table as in mmpc_tick_prepare_device; MOVE: d_start and d_traj_ref are that
+ *      call's nearest-row window; APPROACH and ROTATE (calcLocalRefPose, :398-410): traj_ref[k] = g for k = 0..N with column 2
+ *      replaced by x2 + angleDiff(g2, x2), start = nglob - 1.  The input reference stays the caller's (the plan's u_ref is zero);
+ *   4. d_phase[b] = p; for p < 3 the robot is appended to d_lists[p] (row p of the [3][B] array) at atomicAdd(&d_counts[p], 1), for
+ *      p == 3 d_counts[3] is incremented.  Order inside a list is unspecified; entries beyond a count are not written.
+ * A mission tick is this call on the 'move' handle followed by mmpc_solve_rows_device(h_p, B, d_lists + p B, d_counts + p, B, ...)
+ * on the handles of the three phases, all into one output set at disjoint rows (fleet.py:DeviceFleet.run_mission). */
+int mmpc_mission_prepare_device(mmpc_handle h, int B, double *d_x, long long *d_tick, int *d_phase, const double *d_U_prev,
+                                const double *d_glob, int nglob, const double *d_obs0, const double *d_vel, double *d_x_in,
+                                double *d_traj_ref, int *d_start, double *d_obs, int *d_lists, int *d_counts, void *stream);
 
 /* Streams and threads: a handle owns device state that its launches read and write (parameter block, schedule hint,
  * warm start).  Calls on one handle must come from one host thread at a time.  Launches may use different streams:

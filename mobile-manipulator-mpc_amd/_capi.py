@@ -10,6 +10,7 @@ LIB_PATH = os.environ.get("MMPC_LIB") or os.path.join(_HERE, "csrc", "libmmpc.so
 
 KIND_WHOLEBODY, KIND_BASE, KIND_WHOLEBODY_POSE = 0, 1, 2
 STATUS_CONVERGED, STATUS_MAXITER, STATUS_NUMERIC, STATUS_SUSPENDED = 0, 1, 2, 3
+PHASE_MOVE, PHASE_APPROACH, PHASE_ROTATE, PHASE_DONE = 0, 1, 2, 3      # MMPC_PHASE_*: mission_prepare
 STATUS_Q8_REFUSED = 8      # host-side only (controllers/_q8.py): converged, but an as-written extra half-space row is violated
 
 
@@ -25,6 +26,7 @@ EXPORTS = ["mmpc_create", "mmpc_destroy", "mmpc_set_weights", "mmpc_set_terminal
            "mmpc_solve_batch", "mmpc_solve_batch_device", "mmpc_get_u_latest", "mmpc_set_u_latest",
            "mmpc_lds_bytes", "mmpc_problems_per_cu", "mmpc_set_warm_start", "mmpc_set_schedule_hint", "mmpc_set_iteration_budget", "mmpc_resume_batch_device", "mmpc_solve_list_device", "mmpc_suspended_count", "mmpc_last_error", "mmpc_version", "mmpc_ik_batch", "mmpc_ik_batch_device",
            "mmpc_tick_prepare_device", "mmpc_set_obstacle_clock", "mmpc_set_objective_scaling",
+           "mmpc_mission_prepare_device", "mmpc_solve_rows_device",
            "mmpc_shape_supported", "mmpc_load_shape_library", "mmpc_runs_specialised"]
 LISTED_SHAPES = ((KIND_WHOLEBODY, 20, 5), (KIND_WHOLEBODY, 30, 8), (KIND_WHOLEBODY, 20, 3), (KIND_BASE, 15, 3))   # MMPC_FAST_LIST
 
@@ -72,6 +74,8 @@ def lib():
         L.mmpc_ik_batch.argtypes = [C.c_int, C.c_int, _dp, _dp, _dp, _ip, _ip]
         L.mmpc_ik_batch_device.argtypes = [C.c_int, C.c_int] + [C.c_void_p] * 5 + [C.c_void_p]
         L.mmpc_tick_prepare_device.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 8 + [C.c_void_p]
+        L.mmpc_mission_prepare_device.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 5 + [C.c_int] + [C.c_void_p] * 8 + [C.c_void_p]
+        L.mmpc_solve_rows_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 13 + [C.c_void_p]
         L.mmpc_set_obstacle_clock.argtypes = [C.c_void_p, C.c_void_p]
         L.mmpc_set_objective_scaling.argtypes = [C.c_void_p, C.c_double, C.c_void_p]
         L.mmpc_shape_supported.argtypes = [C.c_int, C.c_int, C.c_int]
@@ -342,11 +346,13 @@ class Engine:
         u = np.ascontiguousarray(u, float)
         self._chk(lib().mmpc_set_u_latest(self._h, u.shape[0], _d(u)), "mmpc_set_u_latest")
 
-    def solve_batch_device(self, x_init, traj_ref, u_ref, u_last, obs, x_guess=None, out=None, stream=None, resume=False, rows=None):
+    def solve_batch_device(self, x_init, traj_ref, u_ref, u_last, obs, x_guess=None, out=None, stream=None, resume=False, rows=None,
+                           either_family=False):
         """torch CUDA float64 tensors in / out, asynchronous on torch's current stream (or `stream`).
         PyTorch is only the owner of the device memory and of the stream here.
         rows = (list, count): mmpc_solve_list_device - only the instances list[0 .. count[0]-1] (int32 cuda tensors: a list of
-        row indices and a one-element count, both read on the device) are solved, in list order; the other rows are not touched."""
+        row indices and a one-element count, both read on the device) are solved, in list order; the other rows are not touched.
+        either_family (with rows): mmpc_solve_rows_device - the same on a handle that runs the generic kernel as well; no budget."""
         import torch
         if rows is not None and (out is None or resume):
             raise ValueError("a list launch needs the output set of the whole batch (out=...) and is not a continuation")
@@ -383,9 +389,10 @@ class Engine:
                     raise ValueError("rows = (list, count): contiguous int32 tensors on %s" % dev)
             if cnt.numel() != 1 or lst.numel() < 1:
                 raise ValueError("rows = (list, count): a one-element count and a list of at least one entry")
-            self._chk(lib().mmpc_solve_list_device(self._h, B, p(lst), p(cnt), int(min(lst.numel(), B)), p(x_init), p(traj_ref), p(u_ref), p(u_last),
-                                                   p(x_guess), p(obs), p(out["X"]), p(out["U"]), p(out["s"]), p(out["status"]),
-                                                   p(out["iters"]), p(out["cost"]), p(out["err"]), C.c_void_p(st)), "mmpc_solve_list_device")
+            fn, name = (lib().mmpc_solve_rows_device, "mmpc_solve_rows_device") if either_family else (lib().mmpc_solve_list_device, "mmpc_solve_list_device")
+            self._chk(fn(self._h, B, p(lst), p(cnt), int(min(lst.numel(), B)), p(x_init), p(traj_ref), p(u_ref), p(u_last),
+                         p(x_guess), p(obs), p(out["X"]), p(out["U"]), p(out["s"]), p(out["status"]),
+                         p(out["iters"]), p(out["cost"]), p(out["err"]), C.c_void_p(st)), name)
             return out
         fn = lib().mmpc_resume_batch_device if resume else lib().mmpc_solve_batch_device
         self._chk(fn(self._h, B, p(x_init), p(traj_ref), p(u_ref), p(u_last), p(x_guess),
@@ -393,6 +400,12 @@ class Engine:
                      p(out["iters"]), p(out["cost"]), p(out["err"]), C.c_void_p(st)),
                   "mmpc_resume_batch_device" if resume else "mmpc_solve_batch_device")
         return out
+
+    def solve_rows_device(self, rows, x_init, traj_ref, u_ref, u_last, obs, out, x_guess=None, stream=None):
+        """mmpc_solve_rows_device: rows = (list, count) as in solve_batch_device, on whichever kernel family the handle runs (the
+        generic one included: dense weights, the terminal-xy equality, an unlisted shape); `out` is the output set of the whole
+        batch, of which only the listed rows are written.  RuntimeError (-4) when the handle has an iteration budget set."""
+        return self.solve_batch_device(x_init, traj_ref, u_ref, u_last, obs, x_guess=x_guess, out=out, stream=stream, rows=rows, either_family=True)
 
     def resume_batch_device(self, x_init, traj_ref, u_ref, u_last, obs, out, x_guess=None, stream=None):
         """mmpc_resume_batch_device: continues the instances the preceding budgeted solve_batch_device call (same tensors,
@@ -427,3 +440,31 @@ class Engine:
         p = lambda t_: C.c_void_p(t_.data_ptr()) if t_ is not None else None
         self._chk(lib().mmpc_tick_prepare_device(self._h, B, p(x), p(tick), p(U_prev), p(glob), int(ng), p(obs0), p(vel), p(x_in), p(traj_ref),
                                                  p(start), p(obs), p(u_guess), p(x_guess), C.c_void_p(st)), "mmpc_tick_prepare_device")
+
+    def mission_prepare(self, x, tick, phase, lists, counts, U_prev=None, glob=None, obs0=None, vel=None, x_in=None, traj_ref=None, start=None,
+                        obs=None, stream=None):
+        """mmpc_mission_prepare_device: tick_prepare with the reference's task state machine per robot, asynchronous on torch's
+        current stream (or `stream`).  x (B,9) float64, tick (B,) int64 and phase (B,) int32 (PHASE_*) are updated in place; lists
+        (3,B) int32 receives the rows to solve per phase, counts (4,) int32 the number of robots in each phase (row p of `lists` and
+        counts[p:p+1] are the `rows` of solve_rows_device on phase p's handle).  glob (B,nglob,9) is required; obs0, vel in and x_in,
+        traj_ref, start, obs out as in tick_prepare.  Contiguous cuda tensors on one device."""
+        import torch
+        N, M = self.N, self.M
+        B = x.shape[0]
+        dev = x.device
+        ng = glob.shape[1] if glob is not None and glob.dim() == 3 else 0
+        f64, i64, i32 = torch.float64, torch.int64, torch.int32
+        for name, t_, shp, dt_ in (("x", x, (B, 9), f64), ("tick", tick, (B,), i64), ("phase", phase, (B,), i32), ("lists", lists, (3, B), i32),
+                                   ("counts", counts, (4,), i32), ("U_prev", U_prev, (B, N, 5), f64), ("glob", glob, (B, ng, 9), f64),
+                                   ("obs0", obs0, (B, M, 3), f64), ("vel", vel, (B, M, 2), f64), ("x_in", x_in, (B, 9), f64),
+                                   ("traj_ref", traj_ref, (B, N + 1, 9), f64), ("start", start, (B,), i32), ("obs", obs, (B, N + 1, M, 3), f64)):
+            if t_ is None:
+                if name in ("x", "tick", "phase", "lists", "counts", "glob"):
+                    raise ValueError("%s is required" % name)
+                continue
+            if tuple(t_.shape) != shp or t_.dtype != dt_ or not t_.is_cuda or not t_.is_contiguous() or t_.device != dev:
+                raise ValueError("%s must be a contiguous %s tensor of shape %s on %s" % (name, dt_, shp, dev))
+        st = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
+        p = lambda t_: C.c_void_p(t_.data_ptr()) if t_ is not None else None
+        self._chk(lib().mmpc_mission_prepare_device(self._h, B, p(x), p(tick), p(phase), p(U_prev), p(glob), int(ng), p(obs0), p(vel), p(x_in),
+                                                    p(traj_ref), p(start), p(obs), p(lists), p(counts), C.c_void_p(st)), "mmpc_mission_prepare_device")

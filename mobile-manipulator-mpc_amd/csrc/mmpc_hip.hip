@@ -20,6 +20,7 @@
 #include "mmpc_fast_kernel.h"
 #include "mmpc_ik.h"
 #include "mmpc_tick.h"
+#include "mmpc_mission.h"
 
 template <int KIND, int NC = 0, int MC = -1, int OPSC = -1, int LC = -1>
 __global__ __launch_bounds__(MMPC_WAVE) void mmpc_solve_kernel(
@@ -28,11 +29,13 @@ __global__ __launch_bounds__(MMPC_WAVE) void mmpc_solve_kernel(
     const double *__restrict__ obs, double *__restrict__ X, double *__restrict__ U, double *__restrict__ s,
     int *__restrict__ status, int *__restrict__ iters, double *__restrict__ cost, double *__restrict__ err,
     const int *__restrict__ order, double *__restrict__ soc, int soc_stride, const long long *__restrict__ tick,
-    double scale_max_grad, double *__restrict__ scale_out) {
+    double scale_max_grad, double *__restrict__ scale_out, const int *__restrict__ list_count) {
     extern __shared__ double lds[];
-    if ((int)blockIdx.x >= B) return;
+    // (list launches, mmpc_solve_rows_device: `order` is the caller's list and *list_count its length, both read here)
+    if ((int)blockIdx.x >= (list_count ? *list_count : B)) return;
     // longest-first schedule hint: workgroup i solves instance order[i] (a permutation; results do not depend on it)
     const int b = order ? order[blockIdx.x] : (int)blockIdx.x;
+    if ((unsigned)b >= (unsigned)B) return;
     const MmpcParams &P = *Pp;
     const int N = NC ? NC : P.N, M = MC >= 0 ? MC : P.M;
     // (doubles of an instance's obstacles: the motion record of OPSC = 2 - a constant of the instantiation, see mmpc_solve_one - or the table)
@@ -55,11 +58,12 @@ __global__ __launch_bounds__(MMPC_WAVE) void mmpc_solve_kernel_static(
     const double *__restrict__ obs, double *__restrict__ X, double *__restrict__ U, double *__restrict__ s,
     int *__restrict__ status, int *__restrict__ iters, double *__restrict__ cost, double *__restrict__ err,
     const int *__restrict__ order, double *__restrict__ soc, int soc_stride, const long long *__restrict__ tick,
-    double scale_max_grad, double *__restrict__ scale_out) {
+    double scale_max_grad, double *__restrict__ scale_out, const int *__restrict__ list_count) {
     constexpr int NHS = (KIND == 0 && LC > 0) ? 6 : 0, NQ = (KIND == 0 && AWC && LC >= 2) ? 6 * (LC - 1) : 0;
     __shared__ double lds[mmpc_layout<KIND>(NC, MC, OPSC, NHS, NQ).total];
-    if ((int)blockIdx.x >= B) return;
+    if ((int)blockIdx.x >= (list_count ? *list_count : B)) return;
     const int b = order ? order[blockIdx.x] : (int)blockIdx.x;
+    if ((unsigned)b >= (unsigned)B) return;
     const MmpcParams &P = *Pp;
     constexpr int N = NC, M = MC;
     constexpr size_t so = OPSC == 2 ? (size_t)M * 5 : (size_t)(OPSC ? N + 1 : 1) * M * 3;
@@ -227,7 +231,7 @@ __global__ void mmpc_cold_xguess(int B, int NS, int NX, int clip, const MmpcPara
 // the signature of mmpc_solve_kernel<> and mmpc_solve_kernel_static<> (that of mmpc_fast_kernel<>: mmpc_fast_fn, mmpc_fast_kernel.h)
 typedef void (*mmpc_gen_fn)(const MmpcParams *, int, const double *, const double *, const double *, const double *, const double *,
                             const double *, double *, double *, double *, int *, int *, double *, double *, const int *, double *, int,
-                            const long long *, double, double *);
+                            const long long *, double, double *, const int *);
 
 struct mmpc_handle_s {
     mmpc_config cfg;
@@ -605,14 +609,16 @@ struct MmpcBatch {
     double *cost, *err;
 };
 // what a launch covers: the whole batch, the instances the budgeted launch before it left suspended (a continuation), or the
-// rows of a caller's device list (list launches only: `count` on the device, the grid is `capacity`)
+// rows of a caller's device list (list launches only: `count` on the device, the grid is `capacity`; `either_family`: the list may
+// go to the generic kernel as well - mmpc_solve_rows_device)
 enum MmpcCover { MMPC_WHOLE_BATCH, MMPC_CONTINUATION, MMPC_LIST };
 struct MmpcMode {
     MmpcCover cover;
     const int *list, *count;
     int capacity;
+    bool either_family;
 };
-static const MmpcMode whole_batch = {MMPC_WHOLE_BATCH, nullptr, nullptr, 0}, continuation = {MMPC_CONTINUATION, nullptr, nullptr, 0};
+static const MmpcMode whole_batch = {MMPC_WHOLE_BATCH, nullptr, nullptr, 0, false}, continuation = {MMPC_CONTINUATION, nullptr, nullptr, 0, false};
 
 static int launch(mmpc_handle h, int B, const MmpcBatch &a, hipStream_t st, const MmpcMode &mode) {
     const bool resume = mode.cover == MMPC_CONTINUATION;
@@ -628,7 +634,7 @@ static int launch(mmpc_handle h, int B, const MmpcBatch &a, hipStream_t st, cons
     h->resume_B = 0;
     // launch order of the workgroups (results do not depend on it): the iteration counts of the handle's previous launch of
     // this batch size when there are any and the mode allows them, else the a-priori difficulty key of THIS batch's data
-    if (ulist && !use_fast) return fail(h, MMPC_E_UNSUPPORTED, "%s%s", "list launches need a specialised kernel (this (kind, N, M, weights) runs the generic one)");
+    if (ulist && !use_fast && !mode.either_family) return fail(h, MMPC_E_UNSUPPORTED, "%s%s", "list launches need a specialised kernel (this (kind, N, M, weights) runs the generic one)");
     const bool lpt = !resume && !ulist && h->hint_on && !h->no_lpt_env && B <= h->cfg.max_batch && B > 256;
     const bool history = lpt && h->hint_on == 1 && h->order_B == B;
     const int key_planes = (h->cfg.kind == MMPC_KIND_WHOLEBODY && h->hp.L > 0) ? h->hp.L : 0;
@@ -653,9 +659,9 @@ static int launch(mmpc_handle h, int B, const MmpcBatch &a, hipStream_t st, cons
                            resume ? (const int *)nullptr : ucount, h->d_gscr, h->d_soc, h->soc_doubles, h->d_tick,
                            h->scale_max_grad, h->d_scale_out);
     } else
-        hipLaunchKernelGGL(h->gen_fn, dim3(B), dim3(MMPC_WAVE), h->gen_dyn_lds, st, h->dp, B, a.x_init, a.traj, a.uref, a.ulast,
+        hipLaunchKernelGGL(h->gen_fn, dim3(grid), dim3(MMPC_WAVE), h->gen_dyn_lds, st, h->dp, B, a.x_init, a.traj, a.uref, a.ulast,
                            a.xguess, a.obs, a.X, a.U, a.s, a.status, a.iters, a.cost, a.err, order, h->d_soc, h->soc_doubles, h->d_tick,
-                           h->scale_max_grad, h->d_scale_out);
+                           h->scale_max_grad, h->d_scale_out, ucount);
     HIPCHK(h, hipGetLastError());
     if (use_fast && h->budget > 0 && !resume) {
         // who is suspended: compacted list for mmpc_resume_batch_device
@@ -781,7 +787,19 @@ extern "C" int mmpc_solve_list_device(mmpc_handle h, int B, const int *d_list, c
     const MmpcBatch a = {d_x_init, d_traj_ref, d_u_ref, d_u_last, d_x_guess, d_obs, d_X, d_U, d_s, d_status, d_iters, d_cost, d_err};
     if (bad_batch(h, B, a) || !d_list || !d_count || capacity < 1 || capacity > B)
         return fail(h, MMPC_E_ARG, "mmpc_solve_list_device: %s%s", "bad argument (B in 1..max_batch, 1 <= capacity <= B)");
-    return launch_device(h, B, a, stream, MmpcMode{MMPC_LIST, d_list, d_count, capacity});
+    return launch_device(h, B, a, stream, MmpcMode{MMPC_LIST, d_list, d_count, capacity, false});
+}
+
+extern "C" int mmpc_solve_rows_device(mmpc_handle h, int B, const int *d_list, const int *d_count, int capacity, const double *d_x_init,
+                                      const double *d_traj_ref, const double *d_u_ref, const double *d_u_last, const double *d_x_guess,
+                                      const double *d_obs, double *d_X, double *d_U, double *d_s, int *d_status, int *d_iters,
+                                      double *d_cost, double *d_err, void *stream) {
+    const MmpcBatch a = {d_x_init, d_traj_ref, d_u_ref, d_u_last, d_x_guess, d_obs, d_X, d_U, d_s, d_status, d_iters, d_cost, d_err};
+    if (bad_batch(h, B, a) || !d_list || !d_count || capacity < 1 || capacity > B)
+        return fail(h, MMPC_E_ARG, "mmpc_solve_rows_device: %s%s", "bad argument (B in 1..max_batch, 1 <= capacity <= B)");
+    if (h->budget > 0)
+        return fail(h, MMPC_E_UNSUPPORTED, "mmpc_solve_rows_device: %s%s", "the handle has an iteration budget set (continuations belong to mmpc_solve_list_device)");
+    return launch_device(h, B, a, stream, MmpcMode{MMPC_LIST, d_list, d_count, capacity, true});
 }
 
 extern "C" int mmpc_solve_batch(mmpc_handle h, int B, const double *x_init, const double *traj_ref, const double *u_ref,
@@ -946,6 +964,45 @@ extern "C" int mmpc_tick_prepare_device(mmpc_handle h, int B, double *d_x, long 
     if (h->ev_valid && st != h->last_stream) HIPCHK(h, hipStreamWaitEvent(st, h->ev, 0));
     hipLaunchKernelGGL(mmpc_tick_kernel, dim3(B), dim3(MMPC_WAVE), 0, st, h->dp, B, d_x, d_tick, d_U_prev, d_glob, nglob, d_obs0, d_vel, d_x_in,
                        d_traj_ref, d_start, d_obs, d_u_guess, d_x_guess);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipEventRecord(h->ev, st));
+    h->ev_valid = 1; h->last_stream = st;
+    return MMPC_OK;
+}
+
+// ---- the same with the reference's task state machine per robot (mmpc_mission.h): phases, and the per-phase lists of robots to solve
+__global__ __launch_bounds__(MMPC_WAVE) void mmpc_mission_kernel(
+    const MmpcParams *__restrict__ Pp, int B, double *__restrict__ x, long long *__restrict__ tick, int *__restrict__ phase,
+    const double *__restrict__ U_prev, const double *__restrict__ glob, int nglob, const double *__restrict__ obs0,
+    const double *__restrict__ vel, double *__restrict__ x_in, double *__restrict__ traj_ref, int *__restrict__ start,
+    double *__restrict__ obs, int *__restrict__ lists, int *__restrict__ counts) {
+    __shared__ double lds[MMPC_TICK_LDS];
+    const int b = (int)blockIdx.x;
+    if (b >= B) return;
+    mmpc_mission_robot(*Pp, b, B, x, tick, phase, U_prev, glob, nglob, obs0, vel, x_in, traj_ref, start, obs, lists, counts, lds);
+}
+
+extern "C" int mmpc_mission_prepare_device(mmpc_handle h, int B, double *d_x, long long *d_tick, int *d_phase, const double *d_U_prev,
+                                           const double *d_glob, int nglob, const double *d_obs0, const double *d_vel, double *d_x_in,
+                                           double *d_traj_ref, int *d_start, double *d_obs, int *d_lists, int *d_counts, void *stream) {
+    if (!h) return MMPC_E_ARG;
+    if (h->cfg.kind != MMPC_KIND_WHOLEBODY || !h->hp.obs_per_stage)
+        return fail(h, MMPC_E_UNSUPPORTED, "mmpc_mission_prepare_device: %s%s", "needs a whole-body handle (joint-space reference) created with obs_per_stage = 1 or 2");
+    if (h->hp.obs_per_stage == 2 && d_obs)
+        return fail(h, MMPC_E_ARG, "mmpc_mission_prepare_device: %s%s", "d_obs must be NULL on a motion handle (obs_per_stage = 2): the kernels form the centres from the record and the clock");
+    if (B == 0) return MMPC_OK;
+    if (B < 1 || B > h->cfg.max_batch) return fail(h, MMPC_E_ARG, "mmpc_mission_prepare_device: %s%s", "B must be in 0..max_batch");
+    if (!d_x) return fail(h, MMPC_E_ARG, "mmpc_mission_prepare_device: %s%s", "d_x is required");
+    if (!d_phase || !d_lists || !d_counts) return fail(h, MMPC_E_ARG, "mmpc_mission_prepare_device: %s%s", "d_phase, d_lists and d_counts are required");
+    if (!d_tick && (d_U_prev || d_obs)) return fail(h, MMPC_E_ARG, "mmpc_mission_prepare_device: %s%s", "the advance and the obstacle table need d_tick");
+    if (!d_glob || nglob < 1 || nglob > (1 << 24)) return fail(h, MMPC_E_ARG, "mmpc_mission_prepare_device: %s%s", "d_glob is required, nglob must be in 1..2^24");
+    if (d_obs && h->cfg.M > 0 && (!d_obs0 || !d_vel)) return fail(h, MMPC_E_ARG, "mmpc_mission_prepare_device: %s%s", "the obstacle table needs d_obs0 and d_vel");
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    hipStream_t st = (hipStream_t)stream;
+    if (h->ev_valid && st != h->last_stream) HIPCHK(h, hipStreamWaitEvent(st, h->ev, 0));
+    HIPCHK(h, hipMemsetAsync(d_counts, 0, 4 * sizeof(int), st));
+    hipLaunchKernelGGL(mmpc_mission_kernel, dim3(B), dim3(MMPC_WAVE), 0, st, h->dp, B, d_x, d_tick, d_phase, d_U_prev, d_glob, nglob, d_obs0,
+                       d_vel, d_x_in, d_traj_ref, d_start, d_obs, d_lists, d_counts);
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipEventRecord(h->ev, st));
     h->ev_valid = 1; h->last_stream = st;

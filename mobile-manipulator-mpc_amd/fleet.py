@@ -32,6 +32,12 @@ set, filled next to x_in, so that a continuation on the side stream reads the ti
 nlp_scaling="gradient-based" (with nlp_scaling_max_gradient, default 100): IPOPT's objective scaling on every handle of the fleet
 (mmpc_set_objective_scaling; sub-fleets of run_groups and the handles of run_async included).  None: the engine's default, off.
 
+run_mission: the reference's task state machine per robot (interface_wholebody_qref.py:146-197: move -> approach -> rotate -> move
+finish) instead of a fixed number of 'move' ticks.  A tick is one HIP kernel (mmpc_mission_prepare_device, csrc/mmpc_mission.h: plant
+step, state machine, the phase's reference, and per phase a device-side list of the robots in it) and three list launches
+(mmpc_solve_rows_device) on three handles - move as created, approach with the terminal-xy equality, rotate with the equality and the
+weights diag(5,5,5,0,0,1,1,1,1) - into one output set at disjoint rows.  No host synchronisation; a finished robot is frozen.
+
 specialise=False / "cached" / True: every handle of the fleet (sub-fleets of run_groups and the handles of run_async included) is
 created with this value (_capi.prepare_shape): an unlisted (N, M) then runs the specialised kernels of its shape library - which
 also gives it iteration budgets, and with them run_async.  True builds a missing library first: one to two minutes of hipcc.
@@ -205,6 +211,86 @@ class DeviceFleet:
         finally:
             if shifted:
                 eng.set_warm_start(None, 1.0)
+
+    # ---- missions: the task state machine per robot
+    def _mission_handles(self):
+        """[move, approach, rotate]: the states of the reference's one controller in the three phases (:166-167, :175-178; the
+        equality is never dropped again).  In motion mode all three read the lock-step clock."""
+        if not hasattr(self, "_mission_ctrls"):
+            N = self.N
+            app, rot = self._mk(), self._mk()
+            for c in (app, rot):
+                c.opti.subject_to(c.X[N, :2] == c.X_ref[N, :2])
+                if self.motion:
+                    c._engine.set_obstacle_clock(self._clock0)
+            W = np.diag([5, 5, 5, 0, 0, 1, 1, 1, 1])
+            rot.setWeight(P=W, Q=W)
+            self._mission_ctrls = [self.ctrls[0], app, rot]
+        return [c._engine for c in self._mission_ctrls]
+
+    def run_mission(self, T, streams=3, on_tick=None):
+        """T mission ticks.  streams=1: everything on the current stream; streams=3 (default: 0.5 % faster at B = 8192,
+        profiles/fleet_mission.txt): the three list launches of a tick on three streams, forked after the mission kernel and joined
+        before the next one; the results are bitwise the same.  Returns u0 (B,T,5), iters, status (B,T) - zero
+        where a robot was not solved at a tick -, phase (B,T) int32 (the phase a robot was solved in at a tick; 3: not solved),
+        counts (T,4) robots per phase, x and final_phase after the plant step that follows the last tick, all_converged over the
+        solved rows, rounds.  A failed solve does not raise: the robot goes on with what the solve left.
+        on_tick(t, s): called after tick t's solves are queued (and joined), with the tensors of the tick - x, phase, x_in, loc, obs,
+        u_last, U; they are rewritten by the next tick, so a caller that keeps them clones them there."""
+        torch = self.torch
+        if self.warm_start != "reference":
+            raise ValueError("run_mission starts every solve by the reference's protocol: warm_start='shifted' is not available in a mission")
+        if streams not in (1, 3):
+            raise ValueError("streams must be 1 or 3, not %r" % (streams,))
+        B, N, M = self.B, self.N, self.M
+        dev = self.dev
+        engs = self._mission_handles()
+        f64, i32 = self.f64, dict(dtype=torch.int32, device=dev)
+        if not hasattr(self, "_msets"):
+            mkout = lambda: dict(X=torch.zeros((B, N + 1, 9), **f64), U=torch.zeros((B, N, 5), **f64), s=torch.zeros((B, N + 1), **f64),
+                                 status=torch.zeros(B, **i32), iters=torch.zeros(B, **i32), cost=torch.zeros(B, **f64), err=torch.zeros(B, **f64))
+            self._msets = [mkout(), mkout()]
+            self._min = dict(x_in=torch.zeros((B, 9), **f64), loc=torch.zeros((B, N + 1, 9), **f64),
+                             obs=self.rec if self.motion else torch.zeros((B, N + 1, M, 3), **f64), zero=torch.zeros((B, N, 5), **f64),
+                             phase=torch.zeros(B, **i32), lists=torch.zeros((3, B), **i32), counts=torch.zeros(4, **i32))
+            self._mside = [torch.cuda.Stream(device=dev) for _ in range(3)]
+        F = self._min
+        for e in engs:
+            e.set_iteration_budget(0); e.reset()
+        x = self.x0.clone()
+        tick = self._clock0.zero_()[:B] if self.motion else torch.zeros(B, dtype=torch.int64, device=dev)
+        phase, lists, counts = F["phase"].zero_(), F["lists"], F["counts"]
+        tab = dict() if self.motion else dict(obs0=self.obs0, vel=self.vel, obs=F["obs"])
+        hist = torch.zeros((B, T, 5), **f64)
+        its, sts, phs = torch.zeros((B, T), **i32), torch.zeros((B, T), **i32), torch.zeros((B, T), **i32)
+        cnts = torch.zeros((T, 4), **i32)
+        main = torch.cuda.current_stream(dev)
+        prev = None
+        for t in range(T):
+            out = self._msets[t & 1]
+            engs[0].mission_prepare(x, tick, phase, lists, counts, U_prev=prev, glob=self.glob, x_in=F["x_in"], traj_ref=F["loc"], **tab)
+            ul = prev if prev is not None else F["zero"]
+            if streams == 3:
+                ev = torch.cuda.Event(); ev.record(main)
+            for p, e in enumerate(engs):
+                rows = (lists[p], counts[p:p + 1])
+                if streams == 3:
+                    side = self._mside[p]
+                    side.wait_event(ev)
+                    e.solve_rows_device(rows, F["x_in"], F["loc"], self.uref, ul, F["obs"], out, stream=side.cuda_stream)
+                    evp = torch.cuda.Event(); evp.record(side); main.wait_event(evp)
+                else:
+                    e.solve_rows_device(rows, F["x_in"], F["loc"], self.uref, ul, F["obs"], out)
+            prev = out["U"]
+            solved = phase < 3
+            hist[:, t] = torch.where(solved[:, None], prev[:, 0], hist[:, t])
+            its[:, t] = torch.where(solved, out["iters"], its[:, t]); sts[:, t] = torch.where(solved, out["status"], sts[:, t])
+            phs[:, t] = phase; cnts[t] = counts
+            if on_tick is not None:
+                on_tick(t, dict(x=x, phase=phase, x_in=F["x_in"], loc=F["loc"], obs=F["obs"], u_last=ul, U=prev))
+        if prev is not None:
+            engs[0].mission_prepare(x, tick, phase, lists, counts, U_prev=prev, glob=self.glob)     # the plant step after the last tick
+        return dict(u0=hist, iters=its, status=sts, phase=phs, counts=cnts, x=x, final_phase=phase.clone(), all_converged=(sts == 0).all(), rounds=T)
 
     # ---- groups in lock step, out of phase
     def run_groups(self, T, groups=2, priority=True, on_tick=None):

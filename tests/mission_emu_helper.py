@@ -1,0 +1,208 @@
+"""ctypes driver for the host build of the fleet mission kernel (tests/mission_emu/mmpc_mission_emu.cpp), the numpy definition
+of what that kernel computes, and the inputs the CPU and the GPU tests share.  TEST ONLY: never used by the product package."""
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+
+import tick_emu_helper as TH
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+_SRC = os.path.join(_HERE, "mission_emu", "mmpc_mission_emu.cpp")
+_CSRC = os.path.join(_HERE, "..", "mobile-manipulator-mpc_amd", "csrc")
+_DEPS = [_SRC, os.path.join(_HERE, "..", "include", "mmpc.h")] + [os.path.join(_CSRC, f) for f in ("mmpc_mission.h", "mmpc_tick.h", "mmpc_core.h", "mmpc_tile.h")]
+
+MOVE, APPROACH, ROTATE, DONE = 0, 1, 2, 3
+ANGLE_TOL = 0.5 * 3.141592653589793 / 180
+OUTPUTS = ("x_in", "traj_ref", "start", "obs")
+
+
+def build():
+    out = os.path.join(_HERE, "mission_emu", "_build", "libmmpc_mission_emu.so")
+    if not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(f) for f in _DEPS):
+        os.makedirs(os.path.dirname(out), exist_ok=True)
+        subprocess.check_call(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-Wno-unknown-pragmas", "-o", out, _SRC])
+    return out
+
+
+_p = TH._p
+
+
+def prepare(N, M, dt, xlim, x, tick, phase, U_prev=None, glob=None, obs0=None, vel=None, want=OUTPUTS, reverse=False):
+    """The kernel on the host.  x (B,9), tick (B,) and phase (B,) are NOT modified: the new ones come back as "x", "tick" and
+    "phase" beside the outputs named in `want`, "lists" (3,B) and "counts" (4,).  Everything starts at the sentinel -7."""
+    lib = C.CDLL(build())
+    B = x.shape[0]
+    c = lambda a, t=np.float64: None if a is None else np.ascontiguousarray(a, t)
+    x = np.array(x, np.float64, order="C"); tick = np.array(tick, np.int64, order="C"); phase = np.array(phase, np.int32, order="C")
+    U_prev, glob, obs0, vel = c(U_prev), c(glob), c(obs0), c(vel)
+    out = dict(x_in=np.full((B, 9), -7.0), traj_ref=np.full((B, N + 1, 9), -7.0), start=np.full(B, -7, np.int32), obs=np.full((B, N + 1, M, 3), -7.0))
+    lists, counts = np.full((3, B), -7, np.int32), np.full(4, -7, np.int32)
+    g = lambda k: out[k] if k in want else None
+    xl = np.ascontiguousarray(xlim, np.float64)
+    assert xl.shape == (2, 9) and glob.shape[0] == B
+    rc = lib.mmpc_mission_emu_prepare(C.c_int(N), C.c_int(M), C.c_double(dt), _p(xl), C.c_int(B), _p(x), _p(tick, C.c_longlong), _p(phase, C.c_int),
+                                      _p(U_prev), _p(glob), C.c_int(glob.shape[1]), _p(obs0), _p(vel), _p(g("x_in")), _p(g("traj_ref")),
+                                      _p(g("start"), C.c_int), _p(g("obs")), _p(lists, C.c_int), _p(counts, C.c_int), C.c_int(int(reverse)))
+    assert rc == 0
+    res = {k: v for k, v in out.items() if k in want}
+    res.update(x=x, tick=tick, phase=phase, lists=lists, counts=counts)
+    return res
+
+
+# ---- the numpy definition -------------------------------------------------------------------------------------------------------
+def angle_diff(mm):
+    """the package's MPCWholeBody.angleDiff (a method that does not use its object)"""
+    return lambda a, b: mm.MPCWholeBody.angleDiff(None, a, b)
+
+
+def quantities(mm, x, g):
+    """what the state machine compares with its thresholds, for one robot: |dx| - 2, |dy| - 2, d - 0.2, d - 0.01, |dpsi| - tol"""
+    dx, dy = x[0] - g[0], x[1] - g[1]
+    d = np.sqrt(dx * dx + dy * dy)
+    return np.array([abs(dx) - 2, abs(dy) - 2, d - 0.2, d - 0.01, abs(angle_diff(mm)(x[2], g[2])) - ANGLE_TOL])
+
+
+def state_machine(mm, x, g, p):
+    """stateMachineUpdate (interface_wholebody_qref.py:153-197) up to 'move finish', for one robot on its unclipped state"""
+    dx, dy = x[0] - g[0], x[1] - g[1]
+    d = np.sqrt(dx * dx + dy * dy)
+    if p == MOVE and abs(dx) <= 2 and abs(dy) <= 2:
+        p = APPROACH
+    if p in (MOVE, APPROACH) and d <= 0.2:
+        p = ROTATE
+    if p == ROTATE and abs(angle_diff(mm)(x[2], g[2])) <= ANGLE_TOL and d <= 0.01:
+        p = DONE
+    return p
+
+
+def reference(mm, xlim, dt, N, x, tick, phase, glob, obs0, vel):
+    """The mission tick AFTER the advance, in numpy: x (B,9) and tick (B,) are the advanced state, phase (B,) the phases on entry.
+    Rows of robots that are DONE (on entry or now) keep the sentinel -7."""
+    from importlib import import_module
+    iface = import_module(mm.__name__ + ".interface_wholebody_qref")
+    B, M = x.shape[0], obs0.shape[1]
+    r = dict(phase=np.zeros(B, np.int32), x_in=np.full((B, 9), -7.0), traj_ref=np.full((B, N + 1, 9), -7.0), start=np.full(B, -7, np.int32),
+             obs=np.full((B, N + 1, M, 3), -7.0))
+    zero_u = np.zeros((1, glob.shape[1] - 1, 5))
+    for b in range(B):
+        if phase[b] == DONE:
+            r["phase"][b] = DONE
+            continue
+        g = glob[b, -1]
+        p = state_machine(mm, x[b], g, int(phase[b]))
+        r["phase"][b] = p
+        if p == DONE:
+            continue
+        r["x_in"][b] = np.clip(x[b], xlim[0], xlim[1])
+        if p == MOVE:
+            r["traj_ref"][b] = iface.calc_local_ref_traj(x[b], glob[b:b + 1], zero_u, N)[0][0]
+            r["start"][b] = np.argmin(np.linalg.norm(x[b, None, :2] - glob[b, :, :2], axis=1))
+        else:
+            r["traj_ref"][b] = iface.calc_local_ref_pose(x[b], glob[b:b + 1], zero_u, N, angle_diff(mm))[0][0]
+            r["start"][b] = glob.shape[1] - 1
+        k = (tick[b] + np.arange(N + 1))[:, None, None] * dt
+        o = np.repeat(obs0[b][None], N + 1, axis=0).copy()
+        o[..., :2] += vel[b][None] * k
+        r["obs"][b] = o
+    r["rows"] = [np.flatnonzero(r["phase"] == p) for p in range(3)]
+    r["counts"] = np.array([(r["phase"] == p).sum() for p in range(4)], np.int32)
+    return r
+
+
+# ---- inputs ---------------------------------------------------------------------------------------------------------------------
+BRANCHES = ("move", "move->approach", "move->rotate", "move->done", "approach", "approach->rotate", "approach->done", "rotate, heading off",
+            "rotate, position off", "rotate->done", "done")
+_ENTRY = (MOVE, MOVE, MOVE, MOVE, APPROACH, APPROACH, APPROACH, ROTATE, ROTATE, ROTATE, DONE)
+_AFTER = (MOVE, APPROACH, ROTATE, DONE, APPROACH, ROTATE, DONE, ROTATE, ROTATE, DONE, DONE)
+
+
+def branch_inputs(B=512, N=20, M=3, nglob=31, seed=3):
+    """Robot b is drawn for branch b % 11 of BRANCHES: where it stands relative to its goal (the last row of its straight plan of
+    `nglob` rows), how its heading compares with the goal's, and its entry phase.  Goal headings cycle through -pi, pi, 3.1 and a
+    random one; headings near the goal's lie on both sides of it, some a full turn above it (a full turn BELOW is not the same heading
+    to the reference's angleDiff: fmod keeps the sign of a negative argument).  Speeds are small where a threshold is near,
+    so that the branch is the same with and without the advance.  Returns the kernel's inputs and "branch" (B,)."""
+    rng = np.random.default_rng(seed)
+    br = np.arange(B) % len(BRANCHES)
+    goal = np.zeros((B, 9))
+    goal[:, :2] = rng.uniform(-5, 5, (B, 2))
+    gh = np.array([-np.pi, np.pi, 3.1, 0.0])[(np.arange(B) // len(BRANCHES)) % 4]
+    goal[:, 2] = np.where((np.arange(B) // len(BRANCHES)) % 4 == 3, rng.uniform(-3.5, 3.5, B), gh)
+    goal[:, 6:] = rng.uniform([-1.0, -2.0, 0.5], [1.0, -0.5, 2.5], (B, 3))
+    beta = rng.uniform(-np.pi, np.pi, B)
+    dirv = np.stack([np.cos(beta), np.sin(beta)], axis=1)
+    first = goal.copy()
+    first[:, :2] += 6.0 * dirv
+    first[:, 2] = goal[:, 2] + rng.uniform(-1, 1, B)
+    glob = np.ascontiguousarray(np.transpose(np.linspace(first, goal, nglob), (1, 0, 2)))
+    x = np.zeros((B, 9))
+    phase = np.zeros(B, np.int32)
+    U_prev = rng.uniform(-1, 1, (B, N, 5))
+    for b in range(B):
+        k = br[b]
+        phase[b] = _ENTRY[k]
+        u = lambda lo, hi: rng.uniform(lo, hi)
+        ang = u(-np.pi, np.pi)
+        away = np.array([np.cos(ang), np.sin(ang)])
+        near_heading = goal[b, 2] + u(0.0005, 0.003) * rng.choice([-1, 1]) + 2 * np.pi * rng.integers(0, 2)
+        any_heading = u(-3.5, 3.5)
+        speed = 1.5
+        if k == 0:       # outside the box, around the plan
+            pos, psi = goal[b, :2] + u(3.8, 6.0) * dirv[b] + rng.uniform(-0.3, 0.3, 2), any_heading
+        elif k == 1:     # inside the box, away from the goal
+            while True:
+                off = rng.uniform(-1.8, 1.8, 2)
+                if np.hypot(*off) > 0.5:
+                    break
+            pos, psi = goal[b, :2] + off, any_heading
+        elif k in (2, 5):
+            pos, psi, speed = goal[b, :2] + u(0.05, 0.15) * away, any_heading, 0.1
+        elif k in (3, 6, 9):
+            pos, psi, speed = goal[b, :2] + u(0.0, 0.004) * away, near_heading, 1e-3
+        elif k == 4:     # an approaching robot stays one wherever it is, outside the box too
+            pos, psi = goal[b, :2] + u(0.6, 4.0) * away, any_heading
+        elif k == 7:
+            pos, psi, speed = goal[b, :2] + u(0.0, 0.004) * away, goal[b, 2] + u(0.05, 3.0) * rng.choice([-1, 1]), 1e-3
+        elif k == 8:
+            pos, psi, speed = goal[b, :2] + u(0.03, 0.5) * away, near_heading, 0.1
+        else:
+            pos, psi = goal[b, :2] + u(0.0, 6.0) * away, any_heading
+        x[b, :2], x[b, 2] = pos, psi
+        x[b, 3:5] = rng.uniform(-speed, speed, 2)
+        x[b, 5] = rng.uniform(-speed, speed) if k not in (3, 6, 7, 8, 9) else rng.uniform(-1e-3, 1e-3)
+        x[b, 6:] = goal[b, 6:]
+    obs0 = np.concatenate([rng.uniform(-8, 8, (B, M, 2)), rng.uniform(0.2, 0.6, (B, M, 1))], axis=2)
+    vel = rng.uniform(-0.3, 0.3, (B, M, 2))
+    tick = rng.integers(0, 40, B).astype(np.int64)
+    return dict(x=x, tick=tick, phase=phase, U_prev=U_prev, glob=glob, obs0=np.ascontiguousarray(obs0), vel=vel), br
+
+
+def expected_after(branch):
+    return np.array(_AFTER, np.int32)[branch]
+
+
+def mission_fleet(mm, B=16, N=20, dt=0.1, t_move=3.0, seed=5):
+    """The fleet of the mission tests: robots at the origin at rest, base goal 2.9-3.4 m away at a random bearing with a random goal
+    heading, three circle obstacles beside the straight line (zero velocity), the global plan of Interface.globalPlan2D.  Returns
+    x0 (B,9), glob (B,31,9), obs0 (B,3,3), vel (B,3,2) and the endpoint pose targets (B,4) that give Interface these base goals."""
+    from importlib import import_module
+    iface = import_module(mm.__name__ + ".interface_wholebody_qref")
+    rng = np.random.default_rng(seed)
+    x0 = np.zeros((B, 9))
+    r, beta, psi = rng.uniform(2.9, 3.4, B), rng.uniform(-np.pi, np.pi, B), rng.uniform(-np.pi, np.pi, B)
+    base = np.stack([r * np.cos(beta), r * np.sin(beta)], axis=1)
+    pose = np.stack([base[:, 0] + 0.6 * np.cos(psi), base[:, 1] + 0.6 * np.sin(psi), np.full(B, 1.4), psi], axis=1)
+    # the base goal as Interface.__init__ forms it from the pose target (:24-33)
+    xt = np.zeros((B, 9))
+    for b in range(B):
+        g = pose[b]
+        xt[b, :3] = [g[0] - 0.6 * np.cos(g[3]), g[1] - 0.6 * np.sin(g[3]), g[3]]
+    glob, _ = iface.global_plan_2d(x0, xt, t_move, dt)
+    side = np.stack([-np.sin(beta), np.cos(beta)], axis=1)
+    obs0 = np.zeros((B, 3, 3))
+    for m, (frac, sgn) in enumerate(((0.3, 1.0), (0.55, -1.0), (0.8, 1.0))):
+        obs0[:, m, :2] = frac * base + sgn * rng.uniform(1.1, 1.5, B)[:, None] * side
+        obs0[:, m, 2] = rng.uniform(0.2, 0.3, B)
+    return dict(x0=x0, glob=np.ascontiguousarray(glob), obs0=obs0, vel=np.zeros((B, 3, 2)), pose=pose)
