@@ -247,6 +247,12 @@ MMPC_HD int mmpc_fast_state_doubles(int MC) {
     typedef MmpcFastDims<KIND, N> F;
     return F::NPAIR + F::NS + F::NS * F::NX + 2 * MMPC_FCAP + MMPC_NSCAL + MMPC_WAVE * (2 * F::NPASS + 2 * (MC > 0 ? MC : 1) + 8);
 }
+// where the scalars start in the save area (what the park / resume code calls ST_SCAL): behind trajectory, slacks, equality
+// multipliers and filter.  The tests that trace a suspended solve read the scalars from here.
+template <int KIND, int N>
+MMPC_HD constexpr int mmpc_fast_state_scal_offset() {
+    return MmpcFastDims<KIND, N>::NPAIR + MmpcFastDims<KIND, N>::NS + MmpcFastDims<KIND, N>::NS * MmpcFastDims<KIND, N>::NX + 2 * MMPC_FCAP;
+}
 
 // The envelope of the specialised template, in one place: every bound mmpc_solve_fast asserts statically (mmpc_fast.h,
 // mmpc_fast_iter.inc) is a member here, the assertions read these members, and mmpc_fast_shape_ok (below) is their conjunction -
@@ -687,6 +693,7 @@ MMPC_DEV void mmpc_solve_fast(const MmpcParams &P, const MmpcIO io, double *lds 
     // (offsets into io.state; the pointers are formed where they are used so that nothing of this stays live in the loop)
     constexpr int ST_S = NPAIR, ST_LAM = NPAIR + NS, ST_FILT = NPAIR + NS + NS * NX, ST_SCAL = ST_FILT + 2 * MMPC_FCAP,
                   ST_LANE = ST_SCAL + MMPC_NSCAL;
+    static_assert(ST_SCAL == mmpc_fast_state_scal_offset<KIND, N>(), "the exported offset of the scalars is the one used here");
     // ------------------------------------------------------------------ objective scaling (opt-in, a uniform branch): the solve is
     // the solve of sigma f, sigma from the max-norm of the gradient of f at the starting point as it stands here - before the bound
     // push, s = 0 (the slack term adds nothing).  The weights' copies in CST and the slack weight are multiplied once, no read of

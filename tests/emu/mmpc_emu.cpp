@@ -87,15 +87,25 @@ extern "C" int mmpc_emu_solve_fast_budget(int kind, const MmpcParams *P, int B, 
                                           double *X, double *U, double *s, int *status, int *iters, double *cost, double *err,
                                           int budget, double *state, int resume) {
 #define MMPC_FAST_CASE(K, NN, MM) if (kind == K && P->N == NN && P->M == MM) { run_fast<K, NN, MM>(P, B, x_init, traj_ref, u_ref, u_last, x_guess, obs, X, U, s, status, iters, cost, err, 0, budget, state, resume); return 0; }
-    MMPC_FAST_CASE(0, 20, 5) MMPC_FAST_CASE(1, 15, 3)
+    MMPC_FAST_CASE(0, 20, 5) MMPC_FAST_CASE(0, 20, 3) MMPC_FAST_CASE(0, 30, 8) MMPC_FAST_CASE(1, 15, 3)
 #undef MMPC_FAST_CASE
     return -1;
 }
 extern "C" int mmpc_emu_fast_state_doubles(int kind, int N, int M) {
     if (kind == 0 && N == 20) return mmpc_fast_state_doubles<0, 20>(M);
+    if (kind == 0 && N == 30) return mmpc_fast_state_doubles<0, 30>(M);
     if (kind == 1 && N == 15) return mmpc_fast_state_doubles<1, 15>(M);
     return -1;
 }
+// where the MMPC_NSCAL scalars of a suspended solve start in its save area: the kernel's own constant (ST_SCAL of the park / resume
+// code, which asserts that it is this function's value), the same for every M and obstacle mode of a (kind, N)
+extern "C" int mmpc_emu_fast_state_scal_offset(int kind, int N) {
+    if (kind == 0 && N == 20) return mmpc_fast_state_scal_offset<0, 20>();
+    if (kind == 0 && N == 30) return mmpc_fast_state_scal_offset<0, 30>();
+    if (kind == 1 && N == 15) return mmpc_fast_state_scal_offset<1, 15>();
+    return -1;
+}
+extern "C" int mmpc_emu_fcap() { return MMPC_FCAP; }
 extern "C" int mmpc_emu_fast_lds_doubles(int kind, int N, int M, int obs_per_stage) {
     if (kind == 0 && N == 20) return mmpc_fast_layout<0, 20>(M, obs_per_stage).total;
     if (kind == 0 && N == 30) return mmpc_fast_layout<0, 30>(M, obs_per_stage).total;

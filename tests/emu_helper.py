@@ -159,3 +159,79 @@ def solve_fast_budgeted(par, x_init, traj_ref, u_ref, u_last, obs, budget, max_r
         if not (status == 3).any():
             break
     return dict(X=X, U=U, s=s, status=status, iters=iters, cost=cost, err=err), launches
+
+
+# ---- a suspended solve's scalars, launch by launch ------------------------------------------------------------------------------
+# the ten scalars the park / resume code keeps per instance (st_scal[0..9] of mmpc_fast_iter.inc), in its order
+SCALARS = ("mu", "th_max", "th_min", "prox", "it", "nfilt", "filt_init", "nsmall", "delta_last", "delta_prev")
+
+
+def fcap():
+    """MMPC_FCAP: the filter's capacity"""
+    return C.CDLL(build()).mmpc_emu_fcap()
+
+
+def fast_state_scal_offset(kind, N):
+    """where the scalars start in the save area of a suspended solve: the kernel's own constant, not a formula of this file"""
+    off = C.CDLL(build()).mmpc_emu_fast_state_scal_offset(int(kind), int(N))
+    assert off > 0
+    return off
+
+
+def trace_chain(launch, status, state, scal_offset, budget=1, max_launches=4000):
+    """The chain of budgeted launches of one batch: launch(budget, resume) runs one launch of a host build on the caller's output
+    arrays (of which `status` is one) and save areas `state` [B][doubles]; the first launch, then continuations - each again with
+    the budget - until nobody is suspended.  Returns (scal, launches, areas): scal[l, b] = the ten SCALARS instance b parked after
+    launch l, NaN where it was not suspended then; areas[l] = the save areas after launch l, whole (a row that was not suspended
+    then holds what an earlier launch left)."""
+    rows, areas = [], []
+    for l in range(max_launches):
+        launch(int(budget), int(l > 0))
+        susp = status == 3
+        if not susp.any():
+            return (np.array(rows) if rows else np.zeros((0, len(status), len(SCALARS)))), l + 1, areas
+        sc = np.full((len(status), len(SCALARS)), np.nan)
+        sc[susp] = state[susp, scal_offset:scal_offset + len(SCALARS)]
+        rows.append(sc)
+        areas.append(state.copy())
+    raise AssertionError("still suspended after %d launches" % max_launches)
+
+
+class FastRun:
+    """The inputs of one batch on the specialised kernel of the host build (obs: (B, M, 3) static or (B, N+1, M, 3) per stage),
+    bound once: launch() runs one launch - uninterrupted, budgeted or a continuation - on this object's output arrays."""
+
+    def __init__(self, par, x_init, traj_ref, u_ref, u_last, obs, **kw):
+        self.lib = C.CDLL(build(False))
+        c = lambda a: np.ascontiguousarray(a, float)
+        self.inp = [c(x_init), c(traj_ref), c(u_ref), c(u_last), c(obs)]
+        self.B = B = self.inp[0].shape[0]
+        N, nx, nu = par.N, par.nx, par.nu
+        M = self.inp[4].shape[-2]
+        self.prm = make_params(par, M, self.inp[4].ndim == 4, False, **kw)
+        self.kind = 0 if par.kind == "wholebody" else 1
+        sd = self.lib.mmpc_emu_fast_state_doubles(self.kind, N, M)
+        assert sd > 0
+        self.scal_offset = fast_state_scal_offset(self.kind, N)
+        self.state = np.full((B, sd), np.nan)
+        self.out = dict(X=np.zeros((B, N + 1, nx)), U=np.zeros((B, N, nu)), s=np.zeros((B, N + 1)), status=np.zeros(B, np.int32),
+                        iters=np.zeros(B, np.int32), cost=np.zeros(B), err=np.zeros(B))
+
+    def launch(self, budget=0, resume=0):
+        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int))
+        x, tr, ur, ul, ob = self.inp
+        o = self.out
+        rc = self.lib.mmpc_emu_solve_fast_budget(self.kind, C.byref(self.prm), self.B, _p(x), _p(tr), _p(ur), _p(ul), None, _p(ob),
+                                                 _p(o["X"]), _p(o["U"]), _p(o["s"]), ip(o["status"]), ip(o["iters"]), _p(o["cost"]),
+                                                 _p(o["err"]), int(budget), _p(self.state), int(resume))
+        if rc != 0:
+            raise RuntimeError("no specialised instantiation for this configuration")
+        return o
+
+
+def solve_fast_chain(par, x_init, traj_ref, u_ref, u_last, obs, budget=1, **kw):
+    """The budget-1 chain of the specialised kernel (host build): every iteration of every instance is a cut.  Returns the
+    outputs, the scalars scal[l, b] (SCALARS; NaN where instance b was not suspended after launch l) and the number of launches."""
+    r = FastRun(par, x_init, traj_ref, u_ref, u_last, obs, **kw)
+    scal, launches, _ = trace_chain(r.launch, r.out["status"], r.state, r.scal_offset, budget)
+    return r.out, scal, launches

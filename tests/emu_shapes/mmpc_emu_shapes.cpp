@@ -102,6 +102,7 @@ extern "C" int mmpc_emush_solve_fast(int kind, const MmpcParams *P, int B, const
     return 0;
 }
 extern "C" int mmpc_emush_fast_state_doubles() { return mmpc_fast_state_doubles<MMPC_EMUSH_KIND, MMPC_EMUSH_N>(MMPC_EMUSH_M); }
+extern "C" int mmpc_emush_fast_state_scal_offset() { return mmpc_fast_state_scal_offset<MMPC_EMUSH_KIND, MMPC_EMUSH_N>(); }   // (the scalars of the save area)
 extern "C" int mmpc_emush_fast_lds_doubles(int obs_per_stage) { return mmpc_fast_layout<MMPC_EMUSH_KIND, MMPC_EMUSH_N>(MMPC_EMUSH_M, obs_per_stage).total; }
 extern "C" int mmpc_emush_lds_doubles(int obs_per_stage) { return mmpc_layout<MMPC_EMUSH_KIND>(MMPC_EMUSH_N, MMPC_EMUSH_M, obs_per_stage, 0, 0).total; }
 extern "C" int mmpc_emush_padmap() { return MmpcFastDims<MMPC_EMUSH_KIND, MMPC_EMUSH_N>::PADMAP ? 1 : 0; }
