@@ -49,6 +49,8 @@ extern "C" {
 #define MMPC_PHASE_APPROACH 1 /* 'approach': inside the 2 m box around the goal - hold the goal pose, terminal-xy equality on */
 #define MMPC_PHASE_ROTATE 2   /* 'rotate': within 0.2 m of the goal - the same with the weights diag(5,5,5,0,0,1,1,1,1) */
 #define MMPC_PHASE_DONE 3     /* 'move finish': reached at 1 cm and 0.5 degrees; the robot is frozen */
+#define MMPC_PHASE_MANIPULATE 4 /* 'manipulate': the arm tracks the joint-space plan to the IK's answer (mmpc_manipulate_prepare_device) */
+#define MMPC_PHASE_MANIP_DONE 5 /* 'manipulate finish': the endpoint is within 1 cm of its pose target; the robot is frozen */
 
 /* Build-time structure of the NLP = constructor arguments of MPCWholeBody.__init__
  * (mpc_wholebody_qref.py:7-23: N, ulim, xlim, dulim, robot.dt) / MPCBase.__init__
@@ -295,6 +297,36 @@ int mmpc_tick_prepare_device(mmpc_handle h, int B, double *d_x, long long *d_tic
 int mmpc_mission_prepare_device(mmpc_handle h, int B, double *d_x, long long *d_tick, int *d_phase, const double *d_U_prev,
                                 const double *d_glob, int nglob, const double *d_obs0, const double *d_vel, double *d_x_in,
                                 double *d_traj_ref, int *d_start, double *d_obs, int *d_lists, int *d_counts, void *stream);
+
+/* The manipulate phase of a mission (interface_wholebody_qref.py:204-226): runs after mmpc_mission_prepare_device in every tick, on
+ * the same d_x, d_tick and d_phase, and takes on the robots that call left at MMPC_PHASE_DONE (which it counts, with every code >= 3,
+ * as frozen).  Handle requirements, argument checks, stream ordering and "no allocation, copy or synchronisation" as there; d_phase,
+ * d_pose [B][4] (the endpoint's pose target x, y, z, psi), d_plan [B][nplan][9], d_list [B] and d_counts [2] (int32) are required,
+ * nplan must be in 2..2^16 (int(t_manipulate / dt) + 1 rows), d_qgoal [B][3] and d_ik_status [B] (int32) may be NULL, and one
+ * hipMemsetAsync of the two counts is queued before the kernel.  Per robot b, with p = d_phase[b] and g = d_pose[b]:
+ *   0. p outside {3, 4}: nothing of the robot is read for output or written; p == 5 increments d_counts[1];
+ *   1. p == 4 on entry and d_U_prev given: advance as in mmpc_tick_prepare_device (the mission kernel froze this robot).  A robot that
+ *      enters with p == 3 was advanced by the mission kernel in the same tick and is not advanced again;
+ *   2. p == 3, the transition, on the unclipped state: tx = sqrt(dx dx + dy dy) + 0.007 with dx = g0 - x0, dy = g1 - x1, tz = g2 -
+ *      (0.606 + 0.333); q_goal = the arm's inverse kinematics from x[6..8] for the target (tx, tz) (as mmpc_ik_batch_device) into
+ *      d_qgoal[b], its status into d_ik_status[b]; d_plan[b][j] = (j / T) (target - x) + x for j < T = nplan - 1 and the target itself
+ *      for j = T, target = (x[0..5], q_goal): np.linspace(x, target, nplan).  A failed IK does not stop the robot: the plan goes to the
+ *      point the solver returned, the status says so.  Then p = 4;
+ *   3. p == 4, finish test on the unclipped state: e = (x0 + (r + b_x) cos x2, x1 + (r + b_x) sin x2, z + b_z), (r, z) the arm's
+ *      endpoint in its own frame; sqrt(sum (e_i - g_i)^2) <= 0.01  =>  p = 5: d_counts[1] is incremented, no outputs, frozen from now
+ *      on.  A comparison with a NaN is false: a non-finite robot keeps its phase;
+ *   4. p == 4 and not finished (calcLocalRefTraj([6, 7, 8])): j = the first plan row that attains the minimum distance to x in columns
+ *      6, 7, 8; d_traj_ref[b][k] = plan[b][min(j + k, nplan - 1)], d_start[b] = j, d_x_in[b] = clip(x), the obstacle table as in
+ *      mmpc_tick_prepare_device (none on a motion handle); the robot is appended to d_list at atomicAdd(&d_counts[0], 1).  Order
+ *      inside the list is unspecified; entries beyond the count are not written;
+ *   5. d_phase[b] = p.
+ * A mission tick with the manipulate phase is mmpc_mission_prepare_device, this call, and mmpc_solve_rows_device on the handles of the
+ * four phases (the fourth: terminal-xy equality, weights diag(500, 500, 500, 0, 0, 1, 1, 1, 1), rows d_list / d_counts), all into one
+ * output set at disjoint rows (fleet.py:DeviceFleet.run_mission(manipulate=...)). */
+int mmpc_manipulate_prepare_device(mmpc_handle h, int B, double *d_x, long long *d_tick, int *d_phase, const double *d_U_prev,
+                                   const double *d_pose, int nplan, double *d_plan, double *d_qgoal, int *d_ik_status,
+                                   const double *d_obs0, const double *d_vel, double *d_x_in, double *d_traj_ref, int *d_start,
+                                   double *d_obs, int *d_list, int *d_counts, void *stream);
 
 /* Streams and threads: a handle owns device state that its launches read and write (parameter block, schedule hint,
  * warm start).  Calls on one handle must come from one host thread at a time.  Launches may use different streams:

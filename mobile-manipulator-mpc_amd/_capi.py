@@ -11,6 +11,7 @@ LIB_PATH = os.environ.get("MMPC_LIB") or os.path.join(_HERE, "csrc", "libmmpc.so
 KIND_WHOLEBODY, KIND_BASE, KIND_WHOLEBODY_POSE = 0, 1, 2
 STATUS_CONVERGED, STATUS_MAXITER, STATUS_NUMERIC, STATUS_SUSPENDED = 0, 1, 2, 3
 PHASE_MOVE, PHASE_APPROACH, PHASE_ROTATE, PHASE_DONE = 0, 1, 2, 3      # MMPC_PHASE_*: mission_prepare
+PHASE_MANIPULATE, PHASE_MANIP_DONE = 4, 5                              # ... and manipulate_prepare
 STATUS_Q8_REFUSED = 8      # host-side only (controllers/_q8.py): converged, but an as-written extra half-space row is violated
 
 
@@ -26,7 +27,7 @@ EXPORTS = ["mmpc_create", "mmpc_destroy", "mmpc_set_weights", "mmpc_set_terminal
            "mmpc_solve_batch", "mmpc_solve_batch_device", "mmpc_get_u_latest", "mmpc_set_u_latest",
            "mmpc_lds_bytes", "mmpc_problems_per_cu", "mmpc_set_warm_start", "mmpc_set_schedule_hint", "mmpc_set_iteration_budget", "mmpc_resume_batch_device", "mmpc_solve_list_device", "mmpc_suspended_count", "mmpc_last_error", "mmpc_version", "mmpc_ik_batch", "mmpc_ik_batch_device",
            "mmpc_tick_prepare_device", "mmpc_set_obstacle_clock", "mmpc_set_objective_scaling",
-           "mmpc_mission_prepare_device", "mmpc_solve_rows_device",
+           "mmpc_mission_prepare_device", "mmpc_manipulate_prepare_device", "mmpc_solve_rows_device",
            "mmpc_shape_supported", "mmpc_load_shape_library", "mmpc_runs_specialised"]
 LISTED_SHAPES = ((KIND_WHOLEBODY, 20, 5), (KIND_WHOLEBODY, 30, 8), (KIND_WHOLEBODY, 20, 3), (KIND_BASE, 15, 3))   # MMPC_FAST_LIST
 
@@ -75,6 +76,7 @@ def lib():
         L.mmpc_ik_batch_device.argtypes = [C.c_int, C.c_int] + [C.c_void_p] * 5 + [C.c_void_p]
         L.mmpc_tick_prepare_device.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 8 + [C.c_void_p]
         L.mmpc_mission_prepare_device.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 5 + [C.c_int] + [C.c_void_p] * 8 + [C.c_void_p]
+        L.mmpc_manipulate_prepare_device.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 5 + [C.c_int] + [C.c_void_p] * 11 + [C.c_void_p]
         L.mmpc_solve_rows_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 13 + [C.c_void_p]
         L.mmpc_set_obstacle_clock.argtypes = [C.c_void_p, C.c_void_p]
         L.mmpc_set_objective_scaling.argtypes = [C.c_void_p, C.c_double, C.c_void_p]
@@ -468,3 +470,35 @@ class Engine:
         p = lambda t_: C.c_void_p(t_.data_ptr()) if t_ is not None else None
         self._chk(lib().mmpc_mission_prepare_device(self._h, B, p(x), p(tick), p(phase), p(U_prev), p(glob), int(ng), p(obs0), p(vel), p(x_in),
                                                     p(traj_ref), p(start), p(obs), p(lists), p(counts), C.c_void_p(st)), "mmpc_mission_prepare_device")
+
+    def manipulate_prepare(self, x, tick, phase, pose, plan, lst, counts, U_prev=None, qgoal=None, ik_status=None, obs0=None, vel=None,
+                           x_in=None, traj_ref=None, start=None, obs=None, stream=None):
+        """mmpc_manipulate_prepare_device: the manipulate phase of a mission tick, after mission_prepare on the same x (B,9), tick (B,)
+        and phase (B,), which are updated in place; asynchronous on torch's current stream (or `stream`).  pose (B,4) float64 is the
+        endpoint's pose target; plan (B,nplan,9) receives a robot's joint-space plan at its transition (PHASE_DONE -> PHASE_MANIPULATE)
+        and is read afterwards, qgoal (B,3) and ik_status (B,) int32 (optional) the IK's answer and status; lst (B,) int32 receives the
+        rows to solve, counts (2,) int32 the robots in PHASE_MANIPULATE and in PHASE_MANIP_DONE ((lst, counts[0:1]) are the `rows` of
+        solve_rows_device on the manipulate handle).  obs0, vel in and x_in, traj_ref, start, obs out as in tick_prepare.  Contiguous
+        cuda tensors on one device."""
+        import torch
+        N, M = self.N, self.M
+        B = x.shape[0]
+        dev = x.device
+        npl = plan.shape[1] if plan is not None and plan.dim() == 3 else 0
+        f64, i64, i32 = torch.float64, torch.int64, torch.int32
+        for name, t_, shp, dt_ in (("x", x, (B, 9), f64), ("tick", tick, (B,), i64), ("phase", phase, (B,), i32), ("pose", pose, (B, 4), f64),
+                                   ("plan", plan, (B, npl, 9), f64), ("lst", lst, (B,), i32), ("counts", counts, (2,), i32),
+                                   ("U_prev", U_prev, (B, N, 5), f64), ("qgoal", qgoal, (B, 3), f64), ("ik_status", ik_status, (B,), i32),
+                                   ("obs0", obs0, (B, M, 3), f64), ("vel", vel, (B, M, 2), f64), ("x_in", x_in, (B, 9), f64),
+                                   ("traj_ref", traj_ref, (B, N + 1, 9), f64), ("start", start, (B,), i32), ("obs", obs, (B, N + 1, M, 3), f64)):
+            if t_ is None:
+                if name in ("x", "tick", "phase", "pose", "plan", "lst", "counts"):
+                    raise ValueError("%s is required" % name)
+                continue
+            if tuple(t_.shape) != shp or t_.dtype != dt_ or not t_.is_cuda or not t_.is_contiguous() or t_.device != dev:
+                raise ValueError("%s must be a contiguous %s tensor of shape %s on %s" % (name, dt_, shp, dev))
+        st = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
+        p = lambda t_: C.c_void_p(t_.data_ptr()) if t_ is not None else None
+        self._chk(lib().mmpc_manipulate_prepare_device(self._h, B, p(x), p(tick), p(phase), p(U_prev), p(pose), int(npl), p(plan), p(qgoal),
+                                                       p(ik_status), p(obs0), p(vel), p(x_in), p(traj_ref), p(start), p(obs), p(lst), p(counts),
+                                                       C.c_void_p(st)), "mmpc_manipulate_prepare_device")

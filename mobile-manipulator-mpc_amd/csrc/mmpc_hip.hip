@@ -21,6 +21,7 @@
 #include "mmpc_ik.h"
 #include "mmpc_tick.h"
 #include "mmpc_mission.h"
+#include "mmpc_manipulate.h"
 
 template <int KIND, int NC = 0, int MC = -1, int OPSC = -1, int LC = -1>
 __global__ __launch_bounds__(MMPC_WAVE) void mmpc_solve_kernel(
@@ -1003,6 +1004,48 @@ extern "C" int mmpc_mission_prepare_device(mmpc_handle h, int B, double *d_x, lo
     HIPCHK(h, hipMemsetAsync(d_counts, 0, 4 * sizeof(int), st));
     hipLaunchKernelGGL(mmpc_mission_kernel, dim3(B), dim3(MMPC_WAVE), 0, st, h->dp, B, d_x, d_tick, d_phase, d_U_prev, d_glob, nglob, d_obs0,
                        d_vel, d_x_in, d_traj_ref, d_start, d_obs, d_lists, d_counts);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipEventRecord(h->ev, st));
+    h->ev_valid = 1; h->last_stream = st;
+    return MMPC_OK;
+}
+
+// ---- the manipulate phase of a mission (mmpc_manipulate.h): the robots the mission kernel left at 'move finish', IK at the transition
+__global__ __launch_bounds__(MMPC_WAVE) void mmpc_manipulate_kernel(
+    const MmpcParams *__restrict__ Pp, int B, double *__restrict__ x, long long *__restrict__ tick, int *__restrict__ phase,
+    const double *__restrict__ U_prev, const double *__restrict__ pose, int nplan, double *plan, double *__restrict__ qgoal,
+    int *__restrict__ ik_status, const double *__restrict__ obs0, const double *__restrict__ vel, double *__restrict__ x_in,
+    double *__restrict__ traj_ref, int *__restrict__ start, double *__restrict__ obs, int *__restrict__ list, int *__restrict__ counts) {
+    __shared__ double lds[MMPC_TICK_LDS];
+    const int b = (int)blockIdx.x;
+    if (b >= B) return;
+    mmpc_manipulate_robot(*Pp, b, B, x, tick, phase, U_prev, pose, nplan, plan, qgoal, ik_status, obs0, vel, x_in, traj_ref, start, obs, list,
+                          counts, lds);
+}
+
+extern "C" int mmpc_manipulate_prepare_device(mmpc_handle h, int B, double *d_x, long long *d_tick, int *d_phase, const double *d_U_prev,
+                                              const double *d_pose, int nplan, double *d_plan, double *d_qgoal, int *d_ik_status,
+                                              const double *d_obs0, const double *d_vel, double *d_x_in, double *d_traj_ref, int *d_start,
+                                              double *d_obs, int *d_list, int *d_counts, void *stream) {
+    if (!h) return MMPC_E_ARG;
+    if (h->cfg.kind != MMPC_KIND_WHOLEBODY || !h->hp.obs_per_stage)
+        return fail(h, MMPC_E_UNSUPPORTED, "mmpc_manipulate_prepare_device: %s%s", "needs a whole-body handle (joint-space reference) created with obs_per_stage = 1 or 2");
+    if (h->hp.obs_per_stage == 2 && d_obs)
+        return fail(h, MMPC_E_ARG, "mmpc_manipulate_prepare_device: %s%s", "d_obs must be NULL on a motion handle (obs_per_stage = 2): the kernels form the centres from the record and the clock");
+    if (B == 0) return MMPC_OK;
+    if (B < 1 || B > h->cfg.max_batch) return fail(h, MMPC_E_ARG, "mmpc_manipulate_prepare_device: %s%s", "B must be in 0..max_batch");
+    if (!d_x) return fail(h, MMPC_E_ARG, "mmpc_manipulate_prepare_device: %s%s", "d_x is required");
+    if (!d_phase || !d_pose || !d_plan || !d_list || !d_counts)
+        return fail(h, MMPC_E_ARG, "mmpc_manipulate_prepare_device: %s%s", "d_phase, d_pose, d_plan, d_list and d_counts are required");
+    if (nplan < 2 || nplan > (1 << 16)) return fail(h, MMPC_E_ARG, "mmpc_manipulate_prepare_device: %s%s", "nplan must be in 2..2^16");
+    if (!d_tick && (d_U_prev || d_obs)) return fail(h, MMPC_E_ARG, "mmpc_manipulate_prepare_device: %s%s", "the advance and the obstacle table need d_tick");
+    if (d_obs && h->cfg.M > 0 && (!d_obs0 || !d_vel)) return fail(h, MMPC_E_ARG, "mmpc_manipulate_prepare_device: %s%s", "the obstacle table needs d_obs0 and d_vel");
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    hipStream_t st = (hipStream_t)stream;
+    if (h->ev_valid && st != h->last_stream) HIPCHK(h, hipStreamWaitEvent(st, h->ev, 0));
+    HIPCHK(h, hipMemsetAsync(d_counts, 0, 2 * sizeof(int), st));
+    hipLaunchKernelGGL(mmpc_manipulate_kernel, dim3(B), dim3(MMPC_WAVE), 0, st, h->dp, B, d_x, d_tick, d_phase, d_U_prev, d_pose, nplan, d_plan,
+                       d_qgoal, d_ik_status, d_obs0, d_vel, d_x_in, d_traj_ref, d_start, d_obs, d_list, d_counts);
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipEventRecord(h->ev, st));
     h->ev_valid = 1; h->last_stream = st;

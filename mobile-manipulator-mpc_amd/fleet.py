@@ -37,6 +37,10 @@ finish) instead of a fixed number of 'move' ticks.  A tick is one HIP kernel (mm
 step, state machine, the phase's reference, and per phase a device-side list of the robots in it) and three list launches
 (mmpc_solve_rows_device) on three handles - move as created, approach with the terminal-xy equality, rotate with the equality and the
 weights diag(5,5,5,0,0,1,1,1,1) - into one output set at disjoint rows.  No host synchronisation; a finished robot is frozen.
+manipulate=dict(pose=..., t_manipulate=...) takes the mission on from 'move finish' (:204-226): a second HIP kernel per tick
+(mmpc_manipulate_prepare_device, csrc/mmpc_manipulate.h: the endpoint target in the arm frame, the arm's inverse kinematics and the
+joint-space plan at the transition, then the finish test and the plan's window in the joint columns) and a fourth list launch on a
+fourth handle - the equality and the weights diag(500,500,500,0,0,1,1,1,1) - until the endpoint is within 1 cm of its pose target.
 
 specialise=False / "cached" / True: every handle of the fleet (sub-fleets of run_groups and the handles of run_async included) is
 created with this value (_capi.prepare_shape): an unlisted (N, M) then runs the specialised kernels of its shape library - which
@@ -213,9 +217,10 @@ class DeviceFleet:
                 eng.set_warm_start(None, 1.0)
 
     # ---- missions: the task state machine per robot
-    def _mission_handles(self):
+    def _mission_handles(self, manipulate=False):
         """[move, approach, rotate]: the states of the reference's one controller in the three phases (:166-167, :175-178; the
-        equality is never dropped again).  In motion mode all three read the lock-step clock."""
+        equality is never dropped again).  In motion mode all three read the lock-step clock.  manipulate: and a fourth, the
+        controller's state in 'manipulate' (:211-215) - the equality still on, the weights diag(500,500,500,0,0,1,1,1,1)."""
         if not hasattr(self, "_mission_ctrls"):
             N = self.N
             app, rot = self._mk(), self._mk()
@@ -226,9 +231,18 @@ class DeviceFleet:
             W = np.diag([5, 5, 5, 0, 0, 1, 1, 1, 1])
             rot.setWeight(P=W, Q=W)
             self._mission_ctrls = [self.ctrls[0], app, rot]
-        return [c._engine for c in self._mission_ctrls]
+        if manipulate and len(self._mission_ctrls) < 4:
+            N = self.N
+            man = self._mk()
+            man.opti.subject_to(man.X[N, :2] == man.X_ref[N, :2])
+            if self.motion:
+                man._engine.set_obstacle_clock(self._clock0)
+            W = np.diag([500, 500, 500, 0, 0, 1, 1, 1, 1])
+            man.setWeight(P=W, Q=W)
+            self._mission_ctrls.append(man)
+        return [c._engine for c in self._mission_ctrls[:4 if manipulate else 3]]
 
-    def run_mission(self, T, streams=3, on_tick=None):
+    def run_mission(self, T, streams=3, on_tick=None, manipulate=None):
         """T mission ticks.  streams=1: everything on the current stream; streams=3 (default: 0.5 % faster at B = 8192,
         profiles/fleet_mission.txt): the three list launches of a tick on three streams, forked after the mission kernel and joined
         before the next one; the results are bitwise the same.  Returns u0 (B,T,5), iters, status (B,T) - zero
@@ -236,7 +250,15 @@ class DeviceFleet:
         counts (T,4) robots per phase, x and final_phase after the plant step that follows the last tick, all_converged over the
         solved rows, rounds.  A failed solve does not raise: the robot goes on with what the solve left.
         on_tick(t, s): called after tick t's solves are queued (and joined), with the tensors of the tick - x, phase, x_in, loc, obs,
-        u_last, U; they are rewritten by the next tick, so a caller that keeps them clones them there."""
+        u_last, U; they are rewritten by the next tick, so a caller that keeps them clones them there.
+        manipulate=dict(pose=(B,4) array, t_manipulate=2.0): the mission goes on from 'move finish' (phase 3) through 'manipulate' (4)
+        to 'manipulate finish' (5, frozen): pose is the endpoint's pose target x, y, z, psi per robot, the joint-space plan has
+        int(t_manipulate / dt) + 1 rows.  A tick is then the mission kernel, the manipulate kernel and four list launches (streams=3:
+        the fourth on a side stream of its own); a robot counts as solved where phase < 3 or phase == 4.  Returned in addition:
+        mcounts (T,2) robots in phases 4 and 5 per tick, qgoal (B,3) and ik_status (B,) int32 of the IK at each robot's transition
+        (-1: no transition yet; a failed IK does not raise, the plan goes to the point the solver returned), plan (B,nplan,9); phase
+        and final_phase carry the codes 4 and 5, counts stays what the mission kernel writes (column 3: every phase >= 3); on_tick
+        also gets plan."""
         torch = self.torch
         if self.warm_start != "reference":
             raise ValueError("run_mission starts every solve by the reference's protocol: warm_start='shifted' is not available in a mission")
@@ -244,7 +266,18 @@ class DeviceFleet:
             raise ValueError("streams must be 1 or 3, not %r" % (streams,))
         B, N, M = self.B, self.N, self.M
         dev = self.dev
-        engs = self._mission_handles()
+        manip = manipulate is not None
+        if manip:
+            pose = np.ascontiguousarray(manipulate["pose"].cpu().numpy() if torch.is_tensor(manipulate["pose"]) else manipulate["pose"], np.float64)
+            if pose.shape != (B, 4):
+                raise ValueError("manipulate['pose'] must have shape %r (x, y, z, psi of the endpoint per robot), not %r" % ((B, 4), pose.shape))
+            t_man = float(manipulate.get("t_manipulate", 2.0))
+            if not t_man >= self.dt:
+                raise ValueError("manipulate['t_manipulate'] must be at least dt = %g (a plan of two rows), not %r" % (self.dt, t_man))
+            nplan = int(t_man / self.dt) + 1
+            if nplan > 1 << 16:
+                raise ValueError("manipulate['t_manipulate'] gives a plan of %d rows; at most 65536" % nplan)
+        engs = self._mission_handles(manip)
         f64, i32 = self.f64, dict(dtype=torch.int32, device=dev)
         if not hasattr(self, "_msets"):
             mkout = lambda: dict(X=torch.zeros((B, N + 1, 9), **f64), U=torch.zeros((B, N, 5), **f64), s=torch.zeros((B, N + 1), **f64),
@@ -255,6 +288,16 @@ class DeviceFleet:
                              phase=torch.zeros(B, **i32), lists=torch.zeros((3, B), **i32), counts=torch.zeros(4, **i32))
             self._mside = [torch.cuda.Stream(device=dev) for _ in range(3)]
         F = self._min
+        if manip:
+            if len(self._mside) < 4:
+                self._mside.append(torch.cuda.Stream(device=dev))
+            if getattr(self, "_manip", None) is None or self._manip["plan"].shape[1] != nplan:
+                self._manip = dict(plan=torch.zeros((B, nplan, 9), **f64), pose=torch.zeros((B, 4), **f64), qgoal=torch.zeros((B, 3), **f64),
+                                   ik_status=torch.zeros(B, **i32), list=torch.zeros(B, **i32), counts=torch.zeros(2, **i32))
+            G = self._manip
+            G["pose"].copy_(torch.from_numpy(pose)); G["plan"].zero_(); G["qgoal"].zero_(); G["ik_status"].fill_(-1)
+            mcnts = torch.zeros((T, 2), **i32)
+            mkw = dict(pose=G["pose"], plan=G["plan"], lst=G["list"], counts=G["counts"], qgoal=G["qgoal"], ik_status=G["ik_status"])
         for e in engs:
             e.set_iteration_budget(0); e.reset()
         x = self.x0.clone()
@@ -269,11 +312,13 @@ class DeviceFleet:
         for t in range(T):
             out = self._msets[t & 1]
             engs[0].mission_prepare(x, tick, phase, lists, counts, U_prev=prev, glob=self.glob, x_in=F["x_in"], traj_ref=F["loc"], **tab)
+            if manip:
+                engs[0].manipulate_prepare(x, tick, phase, U_prev=prev, x_in=F["x_in"], traj_ref=F["loc"], **mkw, **tab)
             ul = prev if prev is not None else F["zero"]
             if streams == 3:
                 ev = torch.cuda.Event(); ev.record(main)
             for p, e in enumerate(engs):
-                rows = (lists[p], counts[p:p + 1])
+                rows = (lists[p], counts[p:p + 1]) if p < 3 else (G["list"], G["counts"][0:1])
                 if streams == 3:
                     side = self._mside[p]
                     side.wait_event(ev)
@@ -282,15 +327,25 @@ class DeviceFleet:
                 else:
                     e.solve_rows_device(rows, F["x_in"], F["loc"], self.uref, ul, F["obs"], out)
             prev = out["U"]
-            solved = phase < 3
+            solved = (phase < 3) | (phase == 4) if manip else phase < 3
             hist[:, t] = torch.where(solved[:, None], prev[:, 0], hist[:, t])
             its[:, t] = torch.where(solved, out["iters"], its[:, t]); sts[:, t] = torch.where(solved, out["status"], sts[:, t])
             phs[:, t] = phase; cnts[t] = counts
+            if manip:
+                mcnts[t] = G["counts"]
             if on_tick is not None:
-                on_tick(t, dict(x=x, phase=phase, x_in=F["x_in"], loc=F["loc"], obs=F["obs"], u_last=ul, U=prev))
+                s = dict(x=x, phase=phase, x_in=F["x_in"], loc=F["loc"], obs=F["obs"], u_last=ul, U=prev)
+                if manip:
+                    s["plan"] = G["plan"]
+                on_tick(t, s)
         if prev is not None:
             engs[0].mission_prepare(x, tick, phase, lists, counts, U_prev=prev, glob=self.glob)     # the plant step after the last tick
-        return dict(u0=hist, iters=its, status=sts, phase=phs, counts=cnts, x=x, final_phase=phase.clone(), all_converged=(sts == 0).all(), rounds=T)
+            if manip:
+                engs[0].manipulate_prepare(x, tick, phase, U_prev=prev, **mkw)                     # ... of the robots in 'manipulate'
+        res = dict(u0=hist, iters=its, status=sts, phase=phs, counts=cnts, x=x, final_phase=phase.clone(), all_converged=(sts == 0).all(), rounds=T)
+        if manip:
+            res.update(mcounts=mcnts, qgoal=G["qgoal"].clone(), ik_status=G["ik_status"].clone(), plan=G["plan"].clone())
+        return res
 
     # ---- groups in lock step, out of phase
     def run_groups(self, T, groups=2, priority=True, on_tick=None):
