@@ -328,6 +328,26 @@ int mmpc_manipulate_prepare_device(mmpc_handle h, int B, double *d_x, long long 
                                    const double *d_obs0, const double *d_vel, double *d_x_in, double *d_traj_ref, int *d_start,
                                    double *d_obs, int *d_list, int *d_counts, void *stream);
 
+/* The shifted warm start of a mission tick: step 6 of mmpc_tick_prepare_device on its own, for fleets whose x_in is written by
+ * mmpc_mission_prepare_device and mmpc_manipulate_prepare_device, which write no guess.  Whole-body handles only
+ * (MMPC_KIND_WHOLEBODY; MMPC_E_UNSUPPORTED on any other kind); N and dt come from the handle; obs_per_stage does not matter, the
+ * call touches no obstacle.  One launch, one 64-lane workgroup per robot b:
+ *   d_u_guess[b][k] = U_prev[b][min(k + 1, N - 1)], k = 0..N-1;
+ *   d_x_guess[b][0] = d_x_in[b], d_x_guess[b][k + 1] = f(d_x_guess[b][k], U_prev[b][min(k + 1, N - 1)]) with the plant step of
+ *   mmpc_tick_prepare_device (every operation rounded on its own): bit for bit what that call writes from the same x_in and U_prev.
+ * d_phase [B] (int32, MMPC_PHASE_*) may be NULL, which means every row; otherwise a robot whose phase is not MOVE, APPROACH, ROTATE
+ * or MANIPULATE - the codes that appear in a solve list - is skipped: none of its rows is read or written.  d_U_prev [B][N][5],
+ * d_x_in [B][9], d_u_guess [B][N][5] and d_x_guess [B][N+1][9] are required; a missing one, d_u_guess == d_U_prev or B > max_batch
+ * is MMPC_E_ARG.  B = 0 is a no-op.  Asynchronous on `stream` and ordered against the handle's other launches as
+ * mmpc_tick_prepare_device is; no allocation, copy or synchronisation inside.  A mission tick with the warm start is:
+ *   1. mmpc_mission_prepare_device;
+ *   2. mmpc_manipulate_prepare_device, when the phase is on;
+ *   3. this call with that tick's d_x_in and the previous tick's d_U as d_U_prev;
+ *   4. mmpc_solve_rows_device with d_x_guess on the handles of the phases, each with d_u_guess registered through
+ *      mmpc_set_warm_start(h, d_u_guess, 0.1) (d_u_last stays the previous d_U: the NLP of the tick is unchanged). */
+int mmpc_shift_guess_device(mmpc_handle h, int B, const int *d_phase, const double *d_U_prev, const double *d_x_in,
+                            double *d_u_guess, double *d_x_guess, void *stream);
+
 /* Streams and threads: a handle owns device state that its launches read and write (parameter block, schedule hint,
  * warm start).  Calls on one handle must come from one host thread at a time.  Launches may use different streams:
  * a launch on another stream than the handle's previous one is ordered after it (event wait), and the entry points

@@ -27,7 +27,7 @@ EXPORTS = ["mmpc_create", "mmpc_destroy", "mmpc_set_weights", "mmpc_set_terminal
            "mmpc_solve_batch", "mmpc_solve_batch_device", "mmpc_get_u_latest", "mmpc_set_u_latest",
            "mmpc_lds_bytes", "mmpc_problems_per_cu", "mmpc_set_warm_start", "mmpc_set_schedule_hint", "mmpc_set_iteration_budget", "mmpc_resume_batch_device", "mmpc_solve_list_device", "mmpc_suspended_count", "mmpc_last_error", "mmpc_version", "mmpc_ik_batch", "mmpc_ik_batch_device",
            "mmpc_tick_prepare_device", "mmpc_set_obstacle_clock", "mmpc_set_objective_scaling",
-           "mmpc_mission_prepare_device", "mmpc_manipulate_prepare_device", "mmpc_solve_rows_device",
+           "mmpc_mission_prepare_device", "mmpc_manipulate_prepare_device", "mmpc_solve_rows_device", "mmpc_shift_guess_device",
            "mmpc_shape_supported", "mmpc_load_shape_library", "mmpc_runs_specialised"]
 LISTED_SHAPES = ((KIND_WHOLEBODY, 20, 5), (KIND_WHOLEBODY, 30, 8), (KIND_WHOLEBODY, 20, 3), (KIND_BASE, 15, 3))   # MMPC_FAST_LIST
 
@@ -77,6 +77,7 @@ def lib():
         L.mmpc_tick_prepare_device.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 8 + [C.c_void_p]
         L.mmpc_mission_prepare_device.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 5 + [C.c_int] + [C.c_void_p] * 8 + [C.c_void_p]
         L.mmpc_manipulate_prepare_device.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 5 + [C.c_int] + [C.c_void_p] * 11 + [C.c_void_p]
+        L.mmpc_shift_guess_device.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 5 + [C.c_void_p]
         L.mmpc_solve_rows_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 13 + [C.c_void_p]
         L.mmpc_set_obstacle_clock.argtypes = [C.c_void_p, C.c_void_p]
         L.mmpc_set_objective_scaling.argtypes = [C.c_void_p, C.c_double, C.c_void_p]
@@ -502,3 +503,29 @@ class Engine:
         self._chk(lib().mmpc_manipulate_prepare_device(self._h, B, p(x), p(tick), p(phase), p(U_prev), p(pose), int(npl), p(plan), p(qgoal),
                                                        p(ik_status), p(obs0), p(vel), p(x_in), p(traj_ref), p(start), p(obs), p(lst), p(counts),
                                                        C.c_void_p(st)), "mmpc_manipulate_prepare_device")
+
+    def shift_guess(self, phase, U_prev, x_in, u_guess, x_guess, stream=None):
+        """mmpc_shift_guess_device: the shifted warm start of a mission tick, asynchronous on torch's current stream (or `stream`).
+        U_prev (B,N,5) and x_in (B,9) in; u_guess (B,N,5) = U_prev shifted one stage (the last row twice) and x_guess (B,N+1,9) = the
+        plant's roll-out under it from x_in out, as tick_prepare writes them.  phase (B,) int32 or None (every row): a robot whose
+        phase is not one of 0, 1, 2, 4 is skipped, none of its rows is read or written.  Contiguous cuda tensors on one device."""
+        import torch
+        N = self.N
+        for name, t_ in (("U_prev", U_prev), ("x_in", x_in), ("u_guess", u_guess), ("x_guess", x_guess)):
+            if t_ is None:
+                raise ValueError("%s is required" % name)
+        B = x_in.shape[0]
+        dev = x_in.device
+        f64, i32 = torch.float64, torch.int32
+        for name, t_, shp, dt_ in (("phase", phase, (B,), i32), ("U_prev", U_prev, (B, N, 5), f64), ("x_in", x_in, (B, 9), f64),
+                                   ("u_guess", u_guess, (B, N, 5), f64), ("x_guess", x_guess, (B, N + 1, 9), f64)):
+            if t_ is None:
+                continue
+            if tuple(t_.shape) != shp or t_.dtype != dt_ or not t_.is_cuda or not t_.is_contiguous() or t_.device != dev:
+                raise ValueError("%s must be a contiguous %s tensor of shape %s on %s" % (name, dt_, shp, dev))
+        if u_guess.data_ptr() == U_prev.data_ptr():
+            raise ValueError("u_guess must not be U_prev")
+        st = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
+        p = lambda t_: C.c_void_p(t_.data_ptr()) if t_ is not None else None
+        self._chk(lib().mmpc_shift_guess_device(self._h, B, p(phase), p(U_prev), p(x_in), p(u_guess), p(x_guess), C.c_void_p(st)),
+                  "mmpc_shift_guess_device")

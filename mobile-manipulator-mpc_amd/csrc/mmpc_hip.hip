@@ -22,6 +22,7 @@
 #include "mmpc_tick.h"
 #include "mmpc_mission.h"
 #include "mmpc_manipulate.h"
+#include "mmpc_guess.h"
 
 template <int KIND, int NC = 0, int MC = -1, int OPSC = -1, int LC = -1>
 __global__ __launch_bounds__(MMPC_WAVE) void mmpc_solve_kernel(
@@ -1046,6 +1047,35 @@ extern "C" int mmpc_manipulate_prepare_device(mmpc_handle h, int B, double *d_x,
     HIPCHK(h, hipMemsetAsync(d_counts, 0, 2 * sizeof(int), st));
     hipLaunchKernelGGL(mmpc_manipulate_kernel, dim3(B), dim3(MMPC_WAVE), 0, st, h->dp, B, d_x, d_tick, d_phase, d_U_prev, d_pose, nplan, d_plan,
                        d_qgoal, d_ik_status, d_obs0, d_vel, d_x_in, d_traj_ref, d_start, d_obs, d_list, d_counts);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipEventRecord(h->ev, st));
+    h->ev_valid = 1; h->last_stream = st;
+    return MMPC_OK;
+}
+
+// ---- the shifted warm start of a mission tick (mmpc_guess.h): step 6 of the tick kernel for the robots the tick solves
+__global__ __launch_bounds__(MMPC_WAVE) void mmpc_guess_kernel(
+    const MmpcParams *__restrict__ Pp, int B, const int *__restrict__ phase, const double *__restrict__ U_prev,
+    const double *__restrict__ x_in, double *__restrict__ u_guess, double *__restrict__ x_guess) {
+    const int b = (int)blockIdx.x;
+    if (b >= B) return;
+    mmpc_guess_robot(*Pp, b, phase, U_prev, x_in, u_guess, x_guess);
+}
+
+extern "C" int mmpc_shift_guess_device(mmpc_handle h, int B, const int *d_phase, const double *d_U_prev, const double *d_x_in,
+                                       double *d_u_guess, double *d_x_guess, void *stream) {
+    if (!h) return MMPC_E_ARG;
+    if (h->cfg.kind != MMPC_KIND_WHOLEBODY)
+        return fail(h, MMPC_E_UNSUPPORTED, "mmpc_shift_guess_device: %s%s", "needs a whole-body handle (joint-space reference)");
+    if (B == 0) return MMPC_OK;
+    if (B < 1 || B > h->cfg.max_batch) return fail(h, MMPC_E_ARG, "mmpc_shift_guess_device: %s%s", "B must be in 0..max_batch");
+    if (!d_U_prev || !d_x_in || !d_u_guess || !d_x_guess)
+        return fail(h, MMPC_E_ARG, "mmpc_shift_guess_device: %s%s", "d_U_prev, d_x_in, d_u_guess and d_x_guess are required");
+    if (d_u_guess == d_U_prev) return fail(h, MMPC_E_ARG, "mmpc_shift_guess_device: %s%s", "d_u_guess must not be d_U_prev");
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    hipStream_t st = (hipStream_t)stream;
+    if (h->ev_valid && st != h->last_stream) HIPCHK(h, hipStreamWaitEvent(st, h->ev, 0));
+    hipLaunchKernelGGL(mmpc_guess_kernel, dim3(B), dim3(MMPC_WAVE), 0, st, h->dp, B, d_phase, d_U_prev, d_x_in, d_u_guess, d_x_guess);
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipEventRecord(h->ev, st));
     h->ev_valid = 1; h->last_stream = st;

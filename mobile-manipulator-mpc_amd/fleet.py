@@ -41,6 +41,10 @@ manipulate=dict(pose=..., t_manipulate=...) takes the mission on from 'move fini
 (mmpc_manipulate_prepare_device, csrc/mmpc_manipulate.h: the endpoint target in the arm frame, the arm's inverse kinematics and the
 joint-space plan at the transition, then the finish test and the plan's window in the joint columns) and a fourth list launch on a
 fourth handle - the equality and the weights diag(500,500,500,0,0,1,1,1,1) - until the endpoint is within 1 cm of its pose target.
+run_mission(..., warm_start="shifted"): the shifted warm start of the lock step in a mission.  From tick 1 on a third HIP kernel per
+tick (mmpc_shift_guess_device, csrc/mmpc_guess.h) writes, for the robots the tick solves, the previous optimum shifted one stage and
+its roll-out from the tick's x_in; every list launch starts there, with mu_0 = 0.1 on every handle of the mission.  The NLP of every
+tick is unchanged (U_last stays the previous optimum).  It is a keyword of run_mission, not of the fleet: it needs no fused=True.
 
 specialise=False / "cached" / True: every handle of the fleet (sub-fleets of run_groups and the handles of run_async included) is
 created with this value (_capi.prepare_shape): an unlisted (N, M) then runs the specialised kernels of its shape library - which
@@ -242,7 +246,7 @@ class DeviceFleet:
             self._mission_ctrls.append(man)
         return [c._engine for c in self._mission_ctrls[:4 if manipulate else 3]]
 
-    def run_mission(self, T, streams=3, on_tick=None, manipulate=None):
+    def run_mission(self, T, streams=3, on_tick=None, manipulate=None, warm_start="reference"):
         """T mission ticks.  streams=1: everything on the current stream; streams=3 (default: 0.5 % faster at B = 8192,
         profiles/fleet_mission.txt): the three list launches of a tick on three streams, forked after the mission kernel and joined
         before the next one; the results are bitwise the same.  Returns u0 (B,T,5), iters, status (B,T) - zero
@@ -258,10 +262,21 @@ class DeviceFleet:
         mcounts (T,2) robots in phases 4 and 5 per tick, qgoal (B,3) and ik_status (B,) int32 of the IK at each robot's transition
         (-1: no transition yet; a failed IK does not raise, the plan goes to the point the solver returned), plan (B,nplan,9); phase
         and final_phase carry the codes 4 and 5, counts stays what the mission kernel writes (column 3: every phase >= 3); on_tick
-        also gets plan."""
+        also gets plan.
+        warm_start="reference" (default): every solve starts by the reference's protocol.  "shifted": tick 0 is the reference protocol's;
+        from tick 1 on one more kernel per tick (mmpc_shift_guess_device, after the mission and manipulate kernels, before the
+        launches fork) writes the previous optimum shifted one stage and its roll-out from x_in for the robots the tick solves, every
+        list launch starts there and every handle of the mission runs with mu_0 = 0.1 (set at tick 1 - each handle waits once for its
+        launches in flight, the only host waits of a run - and put back when the run ends, also when on_tick raises).  u_last stays
+        the previous optimum, so the NLP of every tick is the same; the returned dict has the same entries; on_tick also gets u_guess
+        and x_guess (meaningful from tick 1 on, in the rows of the robots solved at that tick)."""
         torch = self.torch
         if self.warm_start != "reference":
-            raise ValueError("run_mission starts every solve by the reference's protocol: warm_start='shifted' is not available in a mission")
+            raise ValueError("a fleet constructed with warm_start='shifted' runs its lock step that way; a mission takes the switch as "
+                             "its own keyword: run_mission(..., warm_start='shifted') on a fleet constructed with the default")
+        if warm_start not in ("reference", "shifted"):
+            raise ValueError("warm_start must be 'reference' or 'shifted', not %r" % (warm_start,))
+        shifted = warm_start == "shifted"
         if streams not in (1, 3):
             raise ValueError("streams must be 1 or 3, not %r" % (streams,))
         B, N, M = self.B, self.N, self.M
@@ -288,6 +303,9 @@ class DeviceFleet:
                              phase=torch.zeros(B, **i32), lists=torch.zeros((3, B), **i32), counts=torch.zeros(4, **i32))
             self._mside = [torch.cuda.Stream(device=dev) for _ in range(3)]
         F = self._min
+        if shifted and "ug" not in F:
+            F.update(ug=torch.zeros((B, N, 5), **f64), xg=torch.zeros((B, N + 1, 9), **f64))
+        ug, xg = (F["ug"], F["xg"]) if shifted else (None, None)
         if manip:
             if len(self._mside) < 4:
                 self._mside.append(torch.cuda.Stream(device=dev))
@@ -309,35 +327,49 @@ class DeviceFleet:
         cnts = torch.zeros((T, 4), **i32)
         main = torch.cuda.current_stream(dev)
         prev = None
-        for t in range(T):
-            out = self._msets[t & 1]
-            engs[0].mission_prepare(x, tick, phase, lists, counts, U_prev=prev, glob=self.glob, x_in=F["x_in"], traj_ref=F["loc"], **tab)
-            if manip:
-                engs[0].manipulate_prepare(x, tick, phase, U_prev=prev, x_in=F["x_in"], traj_ref=F["loc"], **mkw, **tab)
-            ul = prev if prev is not None else F["zero"]
-            if streams == 3:
-                ev = torch.cuda.Event(); ev.record(main)
-            for p, e in enumerate(engs):
-                rows = (lists[p], counts[p:p + 1]) if p < 3 else (G["list"], G["counts"][0:1])
-                if streams == 3:
-                    side = self._mside[p]
-                    side.wait_event(ev)
-                    e.solve_rows_device(rows, F["x_in"], F["loc"], self.uref, ul, F["obs"], out, stream=side.cuda_stream)
-                    evp = torch.cuda.Event(); evp.record(side); main.wait_event(evp)
-                else:
-                    e.solve_rows_device(rows, F["x_in"], F["loc"], self.uref, ul, F["obs"], out)
-            prev = out["U"]
-            solved = (phase < 3) | (phase == 4) if manip else phase < 3
-            hist[:, t] = torch.where(solved[:, None], prev[:, 0], hist[:, t])
-            its[:, t] = torch.where(solved, out["iters"], its[:, t]); sts[:, t] = torch.where(solved, out["status"], sts[:, t])
-            phs[:, t] = phase; cnts[t] = counts
-            if manip:
-                mcnts[t] = G["counts"]
-            if on_tick is not None:
-                s = dict(x=x, phase=phase, x_in=F["x_in"], loc=F["loc"], obs=F["obs"], u_last=ul, U=prev)
+        try:
+            for t in range(T):
+                out = self._msets[t & 1]
+                engs[0].mission_prepare(x, tick, phase, lists, counts, U_prev=prev, glob=self.glob, x_in=F["x_in"], traj_ref=F["loc"], **tab)
                 if manip:
-                    s["plan"] = G["plan"]
-                on_tick(t, s)
+                    engs[0].manipulate_prepare(x, tick, phase, U_prev=prev, x_in=F["x_in"], traj_ref=F["loc"], **mkw, **tab)
+                ul = prev if prev is not None else F["zero"]
+                warm = shifted and prev is not None
+                if warm:
+                    engs[0].shift_guess(phase, prev, F["x_in"], ug, xg)
+                    if t == 1:
+                        for e in engs:
+                            e.set_warm_start(ug, 0.1)        # (waits for the handle's launches in flight: the host waits of a run)
+                kw = dict(x_guess=xg) if warm else {}
+                if streams == 3:
+                    ev = torch.cuda.Event(); ev.record(main)
+                for p, e in enumerate(engs):
+                    rows = (lists[p], counts[p:p + 1]) if p < 3 else (G["list"], G["counts"][0:1])
+                    if streams == 3:
+                        side = self._mside[p]
+                        side.wait_event(ev)
+                        e.solve_rows_device(rows, F["x_in"], F["loc"], self.uref, ul, F["obs"], out, stream=side.cuda_stream, **kw)
+                        evp = torch.cuda.Event(); evp.record(side); main.wait_event(evp)
+                    else:
+                        e.solve_rows_device(rows, F["x_in"], F["loc"], self.uref, ul, F["obs"], out, **kw)
+                prev = out["U"]
+                solved = (phase < 3) | (phase == 4) if manip else phase < 3
+                hist[:, t] = torch.where(solved[:, None], prev[:, 0], hist[:, t])
+                its[:, t] = torch.where(solved, out["iters"], its[:, t]); sts[:, t] = torch.where(solved, out["status"], sts[:, t])
+                phs[:, t] = phase; cnts[t] = counts
+                if manip:
+                    mcnts[t] = G["counts"]
+                if on_tick is not None:
+                    s = dict(x=x, phase=phase, x_in=F["x_in"], loc=F["loc"], obs=F["obs"], u_last=ul, U=prev)
+                    if manip:
+                        s["plan"] = G["plan"]
+                    if shifted:
+                        s.update(u_guess=ug, x_guess=xg)
+                    on_tick(t, s)
+        finally:
+            if shifted:
+                for e in engs:
+                    e.set_warm_start(None, 1.0)
         if prev is not None:
             engs[0].mission_prepare(x, tick, phase, lists, counts, U_prev=prev, glob=self.glob)     # the plant step after the last tick
             if manip:
