@@ -102,6 +102,17 @@ typedef struct mmpc_config {
                           handle's (kind, N, M) has been loaded (mmpc_load_shape_library) before mmpc_create, the handle takes its
                           kernels exactly as it takes a listed shape's; without one it runs the generic kernel.  Ignored for a listed
                           shape, with half-space planes (L > 0) and for the pose-reference kind */
+    int generic_budget; /* 0 (the default): iteration budgets and continuation on the specialised kernels only - a handle whose
+                          (kind, N, M) runs the generic kernel refuses mmpc_set_iteration_budget, a generic launch ignores a
+                          budget.  1: the generic kernel honours the budget too (mmpc_set_iteration_budget: "either family").  The
+                          handle then runs the run-time-sized generic kernel and its continuation twin - not the static-LDS
+                          instantiation of a listed configuration -, with or without a budget: on those configurations the same
+                          solve by another instantiation (equal to rounding, not bit for bit, and slower: profiles/
+                          generic_continuation.txt); everywhere else a handle without a budget is bit for bit a default one.  Save area per instance, allocated at the first budget: the
+                          larger of the two families' states; the generic one is
+                            8 (2 (N+1) nx + N nu + (N+1) + 2 (N+1) R + 64) bytes,  R = 2 nu + 2 nx + M + 4 [whole-body] + 6 [L > 0]
+                            + 6 (L-1) [as written] row slots per stage:  26 264 bytes at (whole-body, N = 30, M = 8).
+                          Any other value is MMPC_E_ARG */
 } mmpc_config;
 
 typedef struct mmpc_handle_s *mmpc_handle;
@@ -145,7 +156,7 @@ int mmpc_solve_batch_device(mmpc_handle h, int B, const double *d_x_init, const 
                             const double *d_obs, double *d_X, double *d_U, double *d_s, int *d_status, int *d_iters,
                             double *d_cost, double *d_err, void *stream);
 
-/* List launch (specialised kernels; no reference counterpart): the same solve for the instances d_list[0 .. *d_count - 1] only -
+/* List launch (specialised kernels, and the generic kernel of a cfg.generic_budget handle; no reference counterpart): the same solve for the instances d_list[0 .. *d_count - 1] only -
  * row indices into the B-row arrays, every index at most once; list and count live in DEVICE memory (the count is read by the
  * kernel: a caller that builds the list on the device never has to synchronise), `capacity` (<= B) bounds the count and is the
  * size of the grid.  An entry outside [0, B) is skipped (nothing can validate a device-side list on the host); a repeated entry is
@@ -154,7 +165,9 @@ int mmpc_solve_batch_device(mmpc_handle h, int B, const double *d_x_init, const 
  * listed instances that need more are suspended as in mmpc_solve_batch_device and mmpc_resume_batch_device (same B) continues
  * exactly them.  What it is for: a receding-horizon loop over many robots in which the robots whose solve is finished advance
  * to their next tick while the few suspended ones are still being continued on another stream (bench.py --config c5).
- * A handle that runs the generic kernel is refused (MMPC_E_UNSUPPORTED): mmpc_solve_rows_device is the list launch for either family. */
+ * A handle that runs the generic kernel is refused (MMPC_E_UNSUPPORTED) unless it was created with cfg.generic_budget, where this
+ * call and mmpc_solve_rows_device are the same launch on either family; mmpc_solve_rows_device is the list launch for either family
+ * on every handle. */
 int mmpc_solve_list_device(mmpc_handle h, int B, const int *d_list, const int *d_count, int capacity, const double *d_x_init,
                            const double *d_traj_ref, const double *d_u_ref, const double *d_u_last, const double *d_x_guess,
                            const double *d_obs, double *d_X, double *d_U, double *d_s, int *d_status, int *d_iters,
@@ -163,7 +176,9 @@ int mmpc_solve_list_device(mmpc_handle h, int B, const int *d_list, const int *d
 /* List launch on whichever kernel the handle runs (no reference counterpart).  Semantics of mmpc_solve_list_device - listed rows
  * only, entries outside [0, B) skipped, unlisted rows neither read nor written, the grid is `capacity` - on a specialised handle (there
  * it IS that launch) and on a generic one: weights the specialised kernels refuse, the terminal-xy equality, an unlisted shape.  No
- * iteration budget: MMPC_E_UNSUPPORTED when the handle has one set (continuations stay with mmpc_solve_list_device).  What it is
+ * iteration budget: MMPC_E_UNSUPPORTED when the handle has one set (continuations stay with mmpc_solve_list_device) - except on a
+ * handle created with cfg.generic_budget, where the budget holds on either family: the listed instances that need more are suspended
+ * and mmpc_resume_batch_device (same B) continues exactly them.  What it is
  * for: the per-phase lists of mmpc_mission_prepare_device, whose 'approach' and 'rotate' handles carry the terminal equality. */
 int mmpc_solve_rows_device(mmpc_handle h, int B, const int *d_list, const int *d_count, int capacity, const double *d_x_init,
                            const double *d_traj_ref, const double *d_u_ref, const double *d_u_last, const double *d_x_guess,
@@ -227,8 +242,8 @@ int mmpc_set_objective_scaling(mmpc_handle h, double max_gradient, double *d_sca
  * Results never depend on the order.  No reference counterpart (the reference solves one instance at a time). */
 int mmpc_set_schedule_hint(mmpc_handle h, int mode);
 
-/* Iteration budget and continuation (specialised kernels only; no reference counterpart - IPOPT runs one instance to the
- * end).  One wave solves one instance, so a launch lasts as long as its slowest instance: a handful of instances that need
+/* Iteration budget and continuation (specialised kernels; the generic kernel on a handle created with cfg.generic_budget - "either
+ * family" below; no reference counterpart - IPOPT runs one instance to the end).  One wave solves one instance, so a launch lasts as long as its slowest instance: a handful of instances that need
  * several hundred iterations (heavy tail of the interior-point iteration count) would hold the results of thousands of
  * finished ones.  With budget > 0, mmpc_solve_batch_device gives every instance at most `budget` iterations per launch;
  * an instance that is not converged by then writes its primal-dual state to the handle (18.7 KB at N=20, M=5) and ends
@@ -239,7 +254,15 @@ int mmpc_set_schedule_hint(mmpc_handle h, int mode);
  * instances the last budgeted launch left suspended.  budget = 0 (default) switches the feature off.
  * A continuation belongs to the budgeted launch directly before it on the handle (same B): after any other launch, a first
  * continuation, mmpc_reset or a change of the budget the save areas are stale and mmpc_resume_batch_device returns
- * MMPC_E_UNSUPPORTED instead of overwriting results with the continuation of an older problem. */
+ * MMPC_E_UNSUPPORTED instead of overwriting results with the continuation of an older problem.
+ * Either family (cfg.generic_budget = 1): the budget is accepted whichever kernel the handle runs, and every launch honours it -
+ * also the launches of a listed shape that go to the generic kernel for dense weights or the terminal-xy equality - through
+ * mmpc_solve_batch_device, mmpc_solve_list_device and mmpc_solve_rows_device alike; the host-pointer mmpc_solve_batch continues
+ * suspended instances at once.  A generic solve parks at the same point of its iteration as a specialised one (after the
+ * termination test, before the barrier update), saves the part of its state that outlives an iteration (size: cfg.generic_budget)
+ * and its continuation is bit for bit the uninterrupted solve of the same handle.  The family must not change between a budgeted
+ * launch and its continuation: mmpc_set_weights and mmpc_set_terminal_xy_equality leave the save areas stale on such a handle
+ * (MMPC_E_UNSUPPORTED from mmpc_resume_batch_device), like the events above.  Without a budget the handle behaves like a default one. */
 int mmpc_set_iteration_budget(mmpc_handle h, int budget);
 int mmpc_resume_batch_device(mmpc_handle h, int B, const double *d_x_init, const double *d_traj_ref, const double *d_u_ref,
                              const double *d_u_last, const double *d_x_guess, const double *d_obs, double *d_X, double *d_U,

@@ -20,7 +20,8 @@ class MmpcConfig(C.Structure):
                 ("max_batch", C.c_int), ("device", C.c_int), ("max_iter", C.c_int),
                 ("dt", C.c_double), ("tol", C.c_double), ("mu_init", C.c_double),
                 ("ulim", (C.c_double * 5) * 2), ("xlim", (C.c_double * 9) * 2), ("dulim", (C.c_double * 5) * 2),
-                ("L", C.c_int), ("halfspace", (C.c_double * 6) * 8), ("as_written", C.c_int), ("specialise", C.c_int)]
+                ("L", C.c_int), ("halfspace", (C.c_double * 6) * 8), ("as_written", C.c_int), ("specialise", C.c_int),
+                ("generic_budget", C.c_int)]
 
 
 EXPORTS = ["mmpc_create", "mmpc_destroy", "mmpc_set_weights", "mmpc_set_terminal_xy_equality", "mmpc_reset",
@@ -163,9 +164,11 @@ class Engine:
     """Owns one mmpc_handle (one controller's NLP structure on one GPU)."""
 
     def __init__(self, kind, N, M, dt, ulim, xlim, dulim, max_batch=1, device=0, obs_per_stage=False,
-                 tol=1e-8, mu_init=1.0, max_iter=2000, halfspaces=None, as_written=False, specialise=False):
+                 tol=1e-8, mu_init=1.0, max_iter=2000, halfspaces=None, as_written=False, specialise=False, generic_budget=False):
         """specialise: False (default), "cached" or True - run the specialised kernels of a shape library for an unlisted
-        (kind, N, M); see prepare_shape (True may compile for one to two minutes)."""
+        (kind, N, M); see prepare_shape (True may compile for one to two minutes).
+        generic_budget: mmpc_config.generic_budget - iteration budgets and continuation on the generic kernel too (set_iteration_budget
+        then succeeds whichever kernel the handle runs; the list launches accept the budget).  False: the specialised kernels only."""
         self.kind, self.N, self.M = kind, int(N), int(M)
         self.nx, self.nu = (6, 2) if kind == KIND_BASE else (9, 5)
         self.nref = 4 if kind == KIND_WHOLEBODY_POSE else self.nx      # reference row: endpoint pose (x,y,z,psi) or the state
@@ -187,6 +190,8 @@ class Engine:
                 cfg.xlim[r][j] = xlim[r, j] if j < self.nx else 0.0
         cfg.L = 0
         cfg.as_written = int(bool(as_written))
+        cfg.generic_budget = int(bool(generic_budget))
+        self.generic_budget = bool(generic_budget)
         cfg.specialise = prepare_shape(kind, N, M, specialise, planes=0 if halfspaces is None else len(halfspaces))
         if halfspaces is not None and len(halfspaces):
             hs = np.asarray(halfspaces, float).reshape(-1, 6)
@@ -301,7 +306,8 @@ class Engine:
         self._chk(lib().mmpc_set_schedule_hint(self._h, int(mode)), "mmpc_set_schedule_hint")
 
     def set_iteration_budget(self, budget):
-        """mmpc_set_iteration_budget: iterations a launch may spend on an instance before it is suspended (0: off)."""
+        """mmpc_set_iteration_budget: iterations a launch may spend on an instance before it is suspended (0: off).  Needs a
+        specialised kernel for the shape, or an engine created with generic_budget."""
         self._chk(lib().mmpc_set_iteration_budget(self._h, int(budget)), "mmpc_set_iteration_budget")
 
     def suspended_count(self):
@@ -355,7 +361,8 @@ class Engine:
         PyTorch is only the owner of the device memory and of the stream here.
         rows = (list, count): mmpc_solve_list_device - only the instances list[0 .. count[0]-1] (int32 cuda tensors: a list of
         row indices and a one-element count, both read on the device) are solved, in list order; the other rows are not touched.
-        either_family (with rows): mmpc_solve_rows_device - the same on a handle that runs the generic kernel as well; no budget."""
+        either_family (with rows): mmpc_solve_rows_device - the same on a handle that runs the generic kernel as well; no budget
+        (an engine created with generic_budget: both list launches take either family and honour the budget)."""
         import torch
         if rows is not None and (out is None or resume):
             raise ValueError("a list launch needs the output set of the whole batch (out=...) and is not a continuation")
@@ -407,7 +414,8 @@ class Engine:
     def solve_rows_device(self, rows, x_init, traj_ref, u_ref, u_last, obs, out, x_guess=None, stream=None):
         """mmpc_solve_rows_device: rows = (list, count) as in solve_batch_device, on whichever kernel family the handle runs (the
         generic one included: dense weights, the terminal-xy equality, an unlisted shape); `out` is the output set of the whole
-        batch, of which only the listed rows are written.  RuntimeError (-4) when the handle has an iteration budget set."""
+        batch, of which only the listed rows are written.  RuntimeError (-4) when the handle has an iteration budget set - unless the
+        engine was created with generic_budget: the budget then holds on either family and resume_batch_device continues the rows."""
         return self.solve_batch_device(x_init, traj_ref, u_ref, u_last, obs, x_guess=x_guess, out=out, stream=stream, rows=rows, either_family=True)
 
     def resume_batch_device(self, x_init, traj_ref, u_ref, u_last, obs, out, x_guess=None, stream=None):

@@ -14,12 +14,14 @@ class MPCBase:
                  ulim=np.array([[-2, -PI], [2, PI]]),
                  xlim=np.array([[-100, -100, -2, -2, -PI], [100, 100, 2, 2, PI]]),
                  max_batch=1, device=0, obs_per_stage=False, n_obstacles=None, tol=1e-8, max_iter=2000,
-                 nlp_scaling=None, nlp_scaling_max_gradient=100.0, specialise=False):
+                 nlp_scaling=None, nlp_scaling_max_gradient=100.0, specialise=False, generic_budget=False):
         """specialise: False (default; an (N, M) other than the built-in (15, 3) runs the generic kernel), "cached" (load the
         shape's library of specialised kernels when it exists and is current, else the generic kernel) or True (build it when
         missing or stale - ONE TO TWO MINUTES of hipcc, once per shape - then load it; ValueError for a shape outside the
         specialised envelope).  See _capi.prepare_shape; a shape library is not always faster than the generic kernel:
-        DESIGN.md section 4 has the measured table."""
+        DESIGN.md section 4 has the measured table.
+        generic_budget: mmpc_config.generic_budget - iteration budgets and continuation also where the handle runs the generic
+        kernel (_capi.Engine); False: on the specialised kernels only."""
         self.Q_value, self.R_value, self.P_value, self.M_value = Q, R, P, M
         self.dt = robot.dt
         self.N = N
@@ -36,7 +38,8 @@ class MPCBase:
         self._engine = _capi.Engine(_capi.KIND_BASE, N, self._M, self.dt, self.ulim, xl,
                                     np.array([[-INF, -INF], [INF, INF]]), max_batch=max_batch, device=device,
                                     obs_per_stage=obs_per_stage, tol=tol, max_iter=max_iter,
-                                    **({} if specialise is False else dict(specialise=specialise)))
+                                    **({} if specialise is False else dict(specialise=specialise)),
+                                    **({} if not generic_budget else dict(generic_budget=True)))
         # nlp_scaling / nlp_scaling_max_gradient: the IPOPT options of these names (the reference leaves them at IPOPT's defaults,
         # "gradient-based" and 100); None leaves the engine as it is created, without scaling (Engine.set_nlp_scaling)
         if nlp_scaling is not None:

@@ -24,7 +24,9 @@ class MPCWholeBody:
                                 [100, 100, INF, 2, 2, PI, PI / 2, 0, PI]]),
                  dulim=np.array([[-INF, -INF, -0.5, -0.5, -0.5], [INF, INF, 0.5, 0.5, 0.5]]),
                  max_batch=1, device=0, n_obstacles=None, tol=1e-8, max_iter=2000,
-                 nlp_scaling=None, nlp_scaling_max_gradient=100.0):
+                 nlp_scaling=None, nlp_scaling_max_gradient=100.0, generic_budget=False):
+        """generic_budget: mmpc_config.generic_budget - iteration budgets and continuation on the generic kernel, the only one this
+        kind runs (_capi.Engine); False: none."""
         self.N = N
         self.Q, self.R, self.P, self.S, self.W = Q, R, P, S, W
         self.dt = robot.dt
@@ -37,7 +39,8 @@ class MPCWholeBody:
             raise ValueError("the kernels bake base_radius 0.4 (base.py:15)")
         self._M = len(obstacle_list) if n_obstacles is None else int(n_obstacles)
         self._engine = _capi.Engine(_capi.KIND_WHOLEBODY_POSE, N, self._M, self.dt, self.ulim, self.xlim, self.dulim,
-                                    max_batch=max_batch, device=device, tol=tol, max_iter=max_iter)
+                                    max_batch=max_batch, device=device, tol=tol, max_iter=max_iter,
+                                    **({} if not generic_budget else dict(generic_budget=True)))
         # nlp_scaling / nlp_scaling_max_gradient: the IPOPT options of these names (the reference leaves them at IPOPT's defaults,
         # "gradient-based" and 100); None leaves the engine as it is created, without scaling (Engine.set_nlp_scaling)
         if nlp_scaling is not None:

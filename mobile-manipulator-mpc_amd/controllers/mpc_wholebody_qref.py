@@ -28,12 +28,14 @@ class MPCWholeBody:
                                 [100, 100, INF, 2, 2, PI, PI / 2, 0, 3 * PI / 2]]),
                  dulim=np.array([[-INF, -INF, -0.5, -0.5, -0.5], [INF, INF, 0.5, 0.5, 0.5]]),
                  max_batch=1, device=0, obs_per_stage=False, n_obstacles=None, tol=1e-8, max_iter=2000,
-                 faithful_convex=None, nlp_scaling=None, nlp_scaling_max_gradient=100.0, specialise=False):
+                 faithful_convex=None, nlp_scaling=None, nlp_scaling_max_gradient=100.0, specialise=False, generic_budget=False):
         """specialise: False (default; an (N, M) outside the four built-in shapes runs the generic kernel), "cached" (load the
         shape's library of specialised kernels when it exists and is current, else the generic kernel) or True (build it when
         missing or stale - ONE TO TWO MINUTES of hipcc, once per shape - then load it; ValueError for a shape outside the
         specialised envelope or with half-space planes).  A built-in shape ignores it.  See _capi.prepare_shape; a shape library is
-        not always faster than the generic kernel: DESIGN.md section 4 has the measured table."""
+        not always faster than the generic kernel: DESIGN.md section 4 has the measured table.
+        generic_budget: mmpc_config.generic_budget - iteration budgets and continuation also where the handle runs the generic
+        kernel (_capi.Engine); False: on the specialised kernels only."""
         self.N = N
         self.Q_value, self.R_value, self.P_value, self.S_value, self.W_value = Q, R, P, S, W
         self.dt = robot.dt
@@ -64,7 +66,8 @@ class MPCWholeBody:
         self._engine = _capi.Engine(_capi.KIND_WHOLEBODY, N, self._M, self.dt, self.ulim, self.xlim, self.dulim,
                                     max_batch=max_batch, device=device, obs_per_stage=obs_per_stage, tol=tol,
                                     max_iter=max_iter, halfspaces=hs, as_written=self._q8_check,
-                                    **({} if specialise is False else dict(specialise=specialise)))
+                                    **({} if specialise is False else dict(specialise=specialise)),
+                                    **({} if not generic_budget else dict(generic_budget=True)))
         # nlp_scaling / nlp_scaling_max_gradient: the IPOPT options of these names (the reference leaves them at IPOPT's defaults,
         # "gradient-based" and 100); None leaves the engine as it is created, without scaling (Engine.set_nlp_scaling)
         if nlp_scaling is not None:

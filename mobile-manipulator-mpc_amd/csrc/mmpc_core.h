@@ -665,7 +665,35 @@ struct MmpcGenRic {
     double nab[NKB], nhm[4];             // next stage's dynamics rows and stage-matrix entries
 };
 
-template <int KIND, int NC = 0, int MC = -1, int OPSC = -1, int LC = -1, int AWC = -1>
+// Save area of a suspended generic solve (iteration budget / continuation, the CONT instantiations of mmpc_solve_one): the part of
+// the LDS slab that outlives an iteration - the iterate, the dynamics' multipliers, slacks and multipliers of every row slot, the
+// filter, the multipliers of the terminal equality, the border variable's words - and MMPC_GEN_NSCAL scalars (the specialised
+// kernels' ten in their order, 10: the objective scaling's factor).  Everything else is recomputed from the launch arguments.
+#define MMPC_GEN_NSCAL 12
+struct MmpcGenState { int X, U, S, LAM, T, Z, FILT, NUEQ, SIGW, SCAL, total; };
+// NX, NU: of the kind; R: row slots per stage (MmpcLayout::R)
+MMPC_HD constexpr MmpcGenState mmpc_gen_state(int NX, int NU, int N, int R) {
+    MmpcGenState g{};
+    int o = 0;
+    g.X = o; o += (N + 1) * NX;
+    g.U = o; o += N * NU;
+    g.S = o; o += N + 1;
+    g.LAM = o; o += (N + 1) * NX;
+    g.T = o; o += (N + 1) * R;
+    g.Z = o; o += (N + 1) * R;
+    g.FILT = o; o += 2 * MMPC_FCAP;
+    g.NUEQ = o; o += 4;
+    g.SIGW = o; o += 16;
+    g.SCAL = o; o += MMPC_GEN_NSCAL;
+    g.total = o;
+    return g;
+}
+
+// CONT: built with the iteration budget / continuation code, as mmpc_solve_fast's (a separate instantiation: the CONT = false
+// kernels carry none of it).  io.budget > 0: an instance that is not finished after that many iterations of this launch writes
+// its state to io.state and ends with status 3; io.resume: the launch starts from that state (same arguments as the launch it
+// continues) and runs exactly the iterations the uninterrupted solve would have run next.
+template <int KIND, int NC = 0, int MC = -1, int OPSC = -1, int LC = -1, int AWC = -1, bool CONT = false>
 MMPC_DEV void mmpc_solve_one(const MmpcParams &P, const MmpcIO io, double *lds MMPC_EMU_ARG) {
     typedef MmpcDims<KIND> D;
     typedef MmpcTab<KIND> TB;
@@ -702,6 +730,8 @@ MMPC_DEV void mmpc_solve_one(const MmpcParams &P, const MmpcIO io, double *lds M
     const bool teq = P.terminal_xy_eq != 0;
     const int SL_UHI = NU, SL_XLO = 2 * NU, SL_XHI = 2 * NU + NX, SL_C = 2 * NU + 2 * NX, SL_S = SL_C + M, SL_H = SL_S + NSELF, SL_Q = SL_H + NHS;
     const double dt = P.dt, tol = P.tol;
+    const bool resume = CONT && io.resume != 0;   // (continuation: everything of the launch arguments is loaded again, the point is not formed)
+    const MmpcGenState GS = mmpc_gen_state(NX, NU, N, R);
     double Sw = P.S, sigma = 1.0;   // (objective scaling: the slack weight becomes P.S sigma; off: sigma is the constant 1 and nothing is multiplied)
 
     // bound of a box slot r at stage k; returns false when the row does not exist
@@ -762,17 +792,20 @@ MMPC_DEV void mmpc_solve_one(const MmpcParams &P, const MmpcIO io, double *lds M
         double x0 = io.x_init[j];
         if (KIND != 1) { const double lo = WTS[MMPC_W_XLIM + j], hi = WTS[MMPC_W_XLIM + 9 + j]; x0 = x0 > hi ? hi : (x0 < lo ? lo : x0); }  // :290-291 (a NaN stays a NaN)
         if (i < NS * NREF) XREF[i] = io.traj_ref[i];
+        if (resume) continue;
         X[i] = (io.x_guess && i >= NX) ? io.x_guess[i] : x0;  // :302 / mpc_base.py:200
         LAM[i] = 0.0;
     }
     for (int i = lane; i < N * NU; i += MMPC_WAVE) {
         UREF[i] = io.u_ref[i];
         ULAST[i] = io.u_last[i];
-        U[i] = io.u_guess ? io.u_guess[i] : io.u_last[i];  // :303,:310
+        if (!resume) U[i] = io.u_guess ? io.u_guess[i] : io.u_last[i];  // :303,:310
     }
+    if (!resume) {
     for (int i = lane; i < NS; i += MMPC_WAVE) S[i] = 0.0;  // :304
     if (lane < 4) NUEQ[lane] = 0.0;
     if (lane < 16) SIGW[lane] = 0.0;
+    }
     if (MOTION) {
         for (int i = lane; i < M * 5; i += MMPC_WAVE) OBS[i] = io.obs[i];
         if (lane == 0) OBS[M * 5] = io.tick ? (double)io.tick[0] : 0.0;
@@ -782,7 +815,11 @@ MMPC_DEV void mmpc_solve_one(const MmpcParams &P, const MmpcIO io, double *lds M
     // ---------------------------------------------------------------- objective scaling (opt-in, a uniform branch): the solve is the
     // solve of sigma f, sigma from the gradient of f at the starting point as it stands here - before the bound push, s = 0 (so
     // the slack term adds nothing).  The weights' copies in WTS and the slack weight are multiplied once; nothing else changes.
+    // A continuation goes on with the factor of ITS solve, from the save area (its iterate is no longer the point the factor came
+    // from); the weights are scaled again from the parameter block by the same expressions.
     if (io.scale_max_grad > 0.0) {
+        if (resume) sigma = MMPC_UNIFORM(io.state[GS.SCAL + 10]);
+        else {
         LANES_BEGIN
         double gm = 0.0;
         for (int k = lane; k < NS; k += MMPC_WAVE) {
@@ -802,6 +839,7 @@ MMPC_DEV void mmpc_solve_one(const MmpcParams &P, const MmpcIO io, double *lds M
         RED[lane] = gm;
         LANES_END
         sigma = MMPC_UNIFORM(mmpc_scale_factor(MMPC_GRED_MAX(RED), io.scale_max_grad));
+        }
         LANES_BEGIN
         for (int i = lane; i < MMPC_W_XLIM; i += MMPC_WAVE)
             WTS[i] = (i >= MMPC_W_RW2 && i < MMPC_W_R2) ? mmpc_scaled_rw2(P.R2[i - MMPC_W_RW2], P.W2[i - MMPC_W_RW2], sigma) : WTS[i] * sigma;
@@ -810,6 +848,7 @@ MMPC_DEV void mmpc_solve_one(const MmpcParams &P, const MmpcIO io, double *lds M
         Sw = MMPC_UNIFORM(P.S * sigma);
     }
     // bound push of the initial point (needs U_last of the previous phase for the merged input box)
+    if (!resume) {
     LANES_BEGIN
     for (int i = lane; i < N * NU; i += MMPC_WAVE) {
         const int k = i / NU, j = i % NU;
@@ -826,6 +865,7 @@ MMPC_DEV void mmpc_solve_one(const MmpcParams &P, const MmpcIO io, double *lds M
         X[i] = mmpc_bound_push(X[i], lo, hi);
     }
     LANES_END
+    }
 
     // value of the non-box rows of stage k at a point (used for slack init and line search)
     // returns via hr[NR]
@@ -853,6 +893,7 @@ MMPC_DEV void mmpc_solve_one(const MmpcParams &P, const MmpcIO io, double *lds M
 
     double mu = P.mu_init;
     // ---------------------------------------------------------------- slack / multiplier init
+    if (!resume) {
     LANES_BEGIN
     for (int k = lane; k < NS; k += MMPC_WAVE) {
         double hr[HRMAX];
@@ -876,6 +917,7 @@ MMPC_DEV void mmpc_solve_one(const MmpcParams &P, const MmpcIO io, double *lds M
         }
     }
     LANES_END
+    }
 
     int status = 1, it = 0, nfilt = 0, filt_init = 0, nrows_act = 0, nsmall = 0;
     double prox = 0.0, delta_last = 0.0, delta_prev = 0.0;   // (delta_prev: the correction of the previous iteration's matrix, 0 when it needed none)
@@ -1010,8 +1052,28 @@ MMPC_DEV void mmpc_solve_one(const MmpcParams &P, const MmpcIO io, double *lds M
     }
     nrows_act += NS * NR - NQ;
 
+    if (resume) {
+        // ---- continue a suspended solve: the state the uninterrupted loop holds at the top of iteration `it` (the evaluation below
+        //      forms the rest of the slab again from it, as it did before the solve was parked)
+        const double *const q = io.state;
+        LANES_BEGIN
+        for (int i = lane; i < NS * NX; i += MMPC_WAVE) { X[i] = q[GS.X + i]; LAM[i] = q[GS.LAM + i]; }
+        for (int i = lane; i < N * NU; i += MMPC_WAVE) U[i] = q[GS.U + i];
+        for (int i = lane; i < NS; i += MMPC_WAVE) S[i] = q[GS.S + i];
+        for (int i = lane; i < NS * R; i += MMPC_WAVE) { T[i] = q[GS.T + i]; Z[i] = q[GS.Z + i]; }
+        for (int i = lane; i < 2 * MMPC_FCAP; i += MMPC_WAVE) FILT[i] = q[GS.FILT + i];
+        if (lane < 4) NUEQ[lane] = q[GS.NUEQ + lane];
+        if (lane < 16) SIGW[lane] = q[GS.SIGW + lane];
+        LANES_END
+        const double *const sc = q + GS.SCAL;
+        mu = MMPC_UNIFORM(sc[0]); th_max = MMPC_UNIFORM(sc[1]); th_min = MMPC_UNIFORM(sc[2]); prox = MMPC_UNIFORM(sc[3]);
+        it = (int)MMPC_UNIFORM(sc[4]); nfilt = (int)MMPC_UNIFORM(sc[5]); filt_init = (int)MMPC_UNIFORM(sc[6]);
+        nsmall = (int)MMPC_UNIFORM(sc[7]); delta_last = MMPC_UNIFORM(sc[8]); delta_prev = MMPC_UNIFORM(sc[9]);
+    }
+    const int it_start = CONT ? it : 0;
+
     MMPC_G0()
-    for (it = 0; it <= P.max_iter; it++) {
+    for (it = it_start; it <= P.max_iter; it++) {
         MMPC_GS(0)
         // ============================================================ E1: evaluation + KKT partials
         MMPC_G2()
@@ -1217,6 +1279,28 @@ MMPC_DEV void mmpc_solve_one(const MmpcParams &P, const MmpcIO io, double *lds M
             status = 2; break; }
         if (E0 <= tol) { status = 0; break; }
         if (it == P.max_iter) break;
+        if (CONT && io.budget > 0 && it - it_start >= io.budget && io.state) {
+            // ---- iteration budget of this launch used up: park the solve (the point has just been evaluated and is not converged; a
+            //      continuation evaluates it again and goes on with the barrier update below).  Filter entries behind nfilt are
+            //      written as 0: what a reset left there is never read again.
+            double *const q = io.state;
+            LANES_BEGIN
+            for (int i = lane; i < NS * NX; i += MMPC_WAVE) { q[GS.X + i] = X[i]; q[GS.LAM + i] = LAM[i]; }
+            for (int i = lane; i < N * NU; i += MMPC_WAVE) q[GS.U + i] = U[i];
+            for (int i = lane; i < NS; i += MMPC_WAVE) q[GS.S + i] = S[i];
+            for (int i = lane; i < NS * R; i += MMPC_WAVE) { q[GS.T + i] = T[i]; q[GS.Z + i] = Z[i]; }
+            for (int i = lane; i < 2 * MMPC_FCAP; i += MMPC_WAVE) q[GS.FILT + i] = i < 2 * nfilt ? FILT[i] : 0.0;
+            if (lane < 4) q[GS.NUEQ + lane] = NUEQ[lane];
+            if (lane < 16) q[GS.SIGW + lane] = SIGW[lane];
+            if (lane == 0) {
+                double *const sc = q + GS.SCAL;
+                sc[0] = mu; sc[1] = th_max; sc[2] = th_min; sc[3] = prox; sc[4] = (double)it; sc[5] = (double)nfilt;
+                sc[6] = (double)filt_init; sc[7] = (double)nsmall; sc[8] = delta_last; sc[9] = delta_prev; sc[10] = sigma; sc[11] = 0.0;
+            }
+            LANES_END
+            status = 3;   // MMPC_STATUS_SUSPENDED
+            break;
+        }
         {
             // barrier schedule (Fiacco-McCormick, as IPOPT's monotone mode)
             bool changed = false;

@@ -50,6 +50,42 @@ __global__ __launch_bounds__(MMPC_WAVE) void mmpc_solve_kernel(
     mmpc_solve_one<KIND, NC, MC, OPSC, LC>(P, io, lds);
 }
 
+// The run-time-sized generic kernel with the iteration budget / continuation code (mmpc_solve_one<.., CONT = true>): what a handle
+// created with cfg.generic_budget launches when a budget is set or suspended instances are continued.  The launch forms are those
+// of mmpc_fast_kernel: a whole batch or a caller's list (`order`, *list_count) with one instance per workgroup, or - resume_count
+// != null - a continuation, whose small grid strides over the compacted list of the suspended instances.
+template <int KIND, int OPSC = -1>
+__global__ __launch_bounds__(MMPC_WAVE) void mmpc_solve_kernel_cont(
+    const MmpcParams *__restrict__ Pp, int B, const double *__restrict__ x_init, const double *__restrict__ traj_ref,
+    const double *__restrict__ u_ref, const double *__restrict__ u_last, const double *__restrict__ x_guess,
+    const double *__restrict__ obs, double *__restrict__ X, double *__restrict__ U, double *__restrict__ s,
+    int *__restrict__ status, int *__restrict__ iters, double *__restrict__ cost, double *__restrict__ err,
+    const int *__restrict__ order, double *__restrict__ soc, int soc_stride, const long long *__restrict__ tick,
+    double scale_max_grad, double *__restrict__ scale_out, const int *__restrict__ list_count, int budget,
+    double *__restrict__ state, int state_stride, const int *__restrict__ resume_count) {
+    extern __shared__ double lds[];
+    const int limit = resume_count ? *resume_count : (list_count ? *list_count : B);
+    for (int w = (int)blockIdx.x; w < limit; w += (int)gridDim.x) {
+        const int b = order ? order[w] : w;
+        // (an index outside the batch - a caller's list is unchecked device memory - is skipped: it would address the save areas too)
+        if ((unsigned)b >= (unsigned)B) { if (!resume_count) break; continue; }
+        const MmpcParams &P = *Pp;
+        const int N = P.N, M = P.M;
+        const size_t so = OPSC == 2 ? (size_t)M * 5 : (size_t)(P.obs_per_stage ? N + 1 : 1) * M * 3;
+        MmpcIO io;
+        mmpc_instance_io<KIND>(io, P, b, N, so, x_init, traj_ref, u_ref, u_last, x_guess, obs, X, U, s, status, iters, cost, err,
+                               soc, soc_stride);
+        if (OPSC == 2 && tick) io.tick = tick + b;
+        io.scale_max_grad = scale_max_grad; if (scale_out) io.scale_out = scale_out + b;
+        io.state = state ? state + (size_t)b * state_stride : nullptr;
+        io.budget = budget;
+        io.resume = (resume_count && state) ? 1 : 0;
+        mmpc_solve_one<KIND, 0, -1, OPSC, -1, -1, true>(P, io, lds);
+        if (!resume_count) break;               // (one instance per workgroup except in a continuation launch)
+        __builtin_amdgcn_s_barrier();           // the next instance reuses the LDS block
+    }
+}
+
 // WPE = waves per SIMD the register allocation is sized for (2: <= 256 registers, only pays when LDS allows >4 problems/CU)
 // The generic kernel for a shape that is a constant of the instantiation (the demo's shapes, MMPC_STATIC_LIST): static LDS block
 // and compile-time layout, as for the specialised kernels below; same code, same results as mmpc_solve_kernel<KIND>.
@@ -235,6 +271,11 @@ typedef void (*mmpc_gen_fn)(const MmpcParams *, int, const double *, const doubl
                             const double *, double *, double *, double *, int *, int *, double *, double *, const int *, double *, int,
                             const long long *, double, double *, const int *);
 
+// the signature of mmpc_solve_kernel_cont<>
+typedef void (*mmpc_gen_cont_fn)(const MmpcParams *, int, const double *, const double *, const double *, const double *, const double *,
+                                 const double *, double *, double *, double *, int *, int *, double *, double *, const int *, double *, int,
+                                 const long long *, double, double *, const int *, int, double *, int, const int *);
+
 struct mmpc_handle_s {
     mmpc_config cfg;
     MmpcParams hp;          // host copy
@@ -243,6 +284,8 @@ struct mmpc_handle_s {
     // the handle's kernels, resolved once by mmpc_create (resolve_kernels)
     mmpc_gen_fn gen_fn;     // generic: mmpc_solve_kernel<kind>, or the shape's static-LDS instantiation (MMPC_STATIC_LIST)
     int gen_dyn_lds;        // dynamic LDS of a gen_fn launch: lds_bytes, or 0 for a static-LDS instantiation
+    mmpc_gen_cont_fn gen_cont_fn;   // cfg.generic_budget: the CONT twin of the run-time-sized generic kernel (gen_fn is then that kernel); else null
+    int gen_state_doubles;  // ... and the save area of an instance it suspends (mmpc_gen_state)
     const long long *d_tick;   // obs_per_stage = 2: the registered clock [max_batch] (mmpc_set_obstacle_clock; null: tick 0)
     double scale_max_grad;     // objective scaling (mmpc_set_objective_scaling): nlp_scaling_max_gradient, 0 = off (the default)
     double *d_scale_out;       // ... and the registered array of the instances' factors [max_batch] (null: not wanted)
@@ -267,6 +310,7 @@ struct mmpc_handle_s {
     int soc_doubles;
     int *d_list, *d_count;  // compacted list of the suspended instances of the last launch
     int resume_B;           // batch size of the budgeted launch whose suspended instances can still be continued (0: nothing to resume)
+    int resume_fast;        // ... and the family that launch ran (1 specialised, 0 generic): its continuation runs the same one
     int no_lpt_env, force_generic_env;   // MMPC_NO_LPT / MMPC_FORCE_GENERIC, read once at create (diagnostics)
     int *d_warm;            // per instance: 1 once a CONVERGED solve has filled its u_latest / x_guess rows
     // device-side state and staging (capacity max_batch)
@@ -434,12 +478,22 @@ static void resolve_kernels(mmpc_handle h) {
     const MmpcParams &p = h->hp;
     h->fast_fn[0] = h->fast_fn[1] = nullptr;   // (no list entry for the shape: no specialised kernel, nothing of its sizes)
     h->fast_lds_bytes = h->state_doubles = h->gscr_doubles = 0;
+    h->gen_state_doubles = 0;
     // (the motion mode has run-time-sized instantiations of its own: the mode is a compile-time constant of every kernel)
     const mmpc_gen_fn by_kind[2][3] = {{mmpc_solve_kernel<0>, mmpc_solve_kernel<1>, mmpc_solve_kernel<2>},
                                        {mmpc_solve_kernel<0, 0, -1, 2>, mmpc_solve_kernel<1, 0, -1, 2>, mmpc_solve_kernel<2, 0, -1, 2>}};
     h->gen_fn = by_kind[p.obs_per_stage == 2][c.kind];
     h->gen_dyn_lds = h->lds_bytes;
-    if (!getenv("MMPC_NO_STATIC_GENERIC")) {
+    h->gen_cont_fn = nullptr;
+    // cfg.generic_budget: budgets and continuation on the generic kernel.  The CONT twins exist for the run-time-sized kernels, and
+    // the handle runs the run-time-sized one without a budget too: a continued solve and the uninterrupted one are then two
+    // instantiations of one template with the same constants (the static-LDS kernels of MMPC_STATIC_LIST are not used)
+    if (c.generic_budget) {
+        const mmpc_gen_cont_fn cont_by_kind[2][3] = {{mmpc_solve_kernel_cont<0>, mmpc_solve_kernel_cont<1>, mmpc_solve_kernel_cont<2>},
+                                                     {mmpc_solve_kernel_cont<0, 2>, mmpc_solve_kernel_cont<1, 2>, mmpc_solve_kernel_cont<2, 2>}};
+        h->gen_cont_fn = cont_by_kind[p.obs_per_stage == 2][c.kind];
+    }
+    if (!c.generic_budget && !getenv("MMPC_NO_STATIC_GENERIC")) {
 #define MMPC_X(K, NN, MM, OO, LL, AA)                                                                                      \
         if (c.kind == K && c.N == NN && c.M == MM && p.obs_per_stage == OO && c.L == LL && p.as_written == AA) {             \
             h->gen_fn = mmpc_solve_kernel_static<K, NN, MM, OO, LL, AA>;                                                     \
@@ -480,6 +534,7 @@ extern "C" int mmpc_create(const mmpc_config *cfg, mmpc_handle *out) {
     if (cfg->N < 1 || cfg->N > 63 || cfg->M < 0 || cfg->M > 16 || cfg->max_batch < 1) return MMPC_E_ARG;
     if (cfg->L < 0 || cfg->L > 8 || (cfg->L > 0 && cfg->kind != MMPC_KIND_WHOLEBODY)) return MMPC_E_ARG;
     if (cfg->obs_per_stage < 0 || cfg->obs_per_stage > 2) return MMPC_E_ARG;
+    if (cfg->generic_budget != 0 && cfg->generic_budget != 1) return MMPC_E_ARG;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || cfg->device < 0 || cfg->device >= ndev) return MMPC_E_NODEVICE;
     mmpc_handle h = new (std::nothrow) mmpc_handle_s();
@@ -512,6 +567,12 @@ extern "C" int mmpc_create(const mmpc_config *cfg, mmpc_handle *out) {
     h->lds_bytes = L.total * (int)sizeof(double);
     if (h->lds_bytes > 160 * 1024) return fail(h, MMPC_E_ARG, "problem needs %s bytes of LDS%s", "more than 163840");
     resolve_kernels(h);
+    if (h->gen_cont_fn) {
+        // (one save area per instance serves both families: the larger of the two states)
+        h->gen_state_doubles = mmpc_gen_state(h->nx, h->nu, cfg->N, L.R).total;
+        if (h->state_doubles < h->gen_state_doubles) h->state_doubles = h->gen_state_doubles;
+        HIPCHK(h, hipFuncSetAttribute((const void *)h->gen_cont_fn, hipFuncAttributeMaxDynamicSharedMemorySize, h->lds_bytes));
+    }
     h->per_cu = h->fast_per_cu = 0;
     if (h->gen_dyn_lds) HIPCHK(h, hipFuncSetAttribute((const void *)h->gen_fn, hipFuncAttributeMaxDynamicSharedMemorySize, h->gen_dyn_lds));
     HIPCHK(h, hipOccupancyMaxActiveBlocksPerMultiprocessor(&h->per_cu, h->gen_fn, MMPC_WAVE, h->gen_dyn_lds));
@@ -578,6 +639,7 @@ extern "C" int mmpc_set_weights(mmpc_handle h, const double *Q, const double *R,
     if (W) for (int i = 0; i < nu; i++) for (int j = 0; j < nu; j++) p.W2[i * nu + j] = W[i * nu + j] + W[j * nu + i];
     if (S >= 0) p.S = S;
     for (int i = 0; i < nu * nu; i++) p.RW2[i] = p.R2[i] + p.W2[i];
+    if (h->gen_cont_fn) h->resume_B = 0;   // (a continuation re-derives the weights: the save areas belong to the old ones)
     HIPCHK(h, hipSetDevice(h->cfg.device));
     return upload_params(h);
 }
@@ -587,6 +649,7 @@ extern "C" int mmpc_set_terminal_xy_equality(mmpc_handle h, int on) {
     if (on && h->cfg.kind == MMPC_KIND_WHOLEBODY_POSE)
         return fail(h, MMPC_E_UNSUPPORTED, "terminal-xy equality%s%s", " is defined on the joint-space reference only (mpc_wholebody_qref.py)");
     h->hp.terminal_xy_eq = on ? 1 : 0;   // handled by the generic kernel (the specialised kernels do not carry it)
+    if (h->gen_cont_fn) h->resume_B = 0;
     HIPCHK(h, hipSetDevice(h->cfg.device));
     return upload_params(h);
 }
@@ -631,12 +694,14 @@ static int launch(mmpc_handle h, int B, const MmpcBatch &a, hipStream_t st, cons
     const bool use_fast = runs_fast(h);
     // a continuation belongs to the budgeted launch right before it (same B, same buffers): anything in between - another
     // launch, a reset, a change of the budget, a first continuation - leaves the save areas and the list stale
-    if (resume && !(use_fast && h->d_state && h->resume_B == B))
-        return fail(h, MMPC_E_UNSUPPORTED, "%s%s", "nothing to resume: the handle's last launch was not a budgeted launch of this batch size on a specialised kernel");
+    const bool gen_cont = !use_fast && h->gen_cont_fn;   // (cfg.generic_budget: the generic kernel of this launch has a CONT twin)
+    if (resume && !((use_fast || gen_cont) && h->d_state && h->resume_B == B && h->resume_fast == (use_fast ? 1 : 0)))
+        return fail(h, MMPC_E_UNSUPPORTED, "%s%s", h->gen_cont_fn ? "nothing to resume: the handle's last launch was not a budgeted launch of this batch size on the kernel family this one would run, or the weights / the terminal equality have changed since"
+                                                                  : "nothing to resume: the handle's last launch was not a budgeted launch of this batch size on a specialised kernel");
     h->resume_B = 0;
     // launch order of the workgroups (results do not depend on it): the iteration counts of the handle's previous launch of
     // this batch size when there are any and the mode allows them, else the a-priori difficulty key of THIS batch's data
-    if (ulist && !use_fast && !mode.either_family) return fail(h, MMPC_E_UNSUPPORTED, "%s%s", "list launches need a specialised kernel (this (kind, N, M, weights) runs the generic one)");
+    if (ulist && !use_fast && !mode.either_family && !gen_cont) return fail(h, MMPC_E_UNSUPPORTED, "%s%s", "list launches need a specialised kernel (this (kind, N, M, weights) runs the generic one)");
     const bool lpt = !resume && !ulist && h->hint_on && !h->no_lpt_env && B <= h->cfg.max_batch && B > 256;
     const bool history = lpt && h->hint_on == 1 && h->order_B == B;
     const int key_planes = (h->cfg.kind == MMPC_KIND_WHOLEBODY && h->hp.L > 0) ? h->hp.L : 0;
@@ -660,17 +725,24 @@ static int launch(mmpc_handle h, int B, const MmpcBatch &a, hipStream_t st, cons
                            cont ? h->state_doubles : 0, resume ? h->d_count : (const int *)nullptr,
                            resume ? (const int *)nullptr : ucount, h->d_gscr, h->d_soc, h->soc_doubles, h->d_tick,
                            h->scale_max_grad, h->d_scale_out);
+    } else if (gen_cont && (resume || h->budget > 0)) {
+        hipLaunchKernelGGL(h->gen_cont_fn, dim3(resume ? (B < MMPC_RESUME_GRID ? B : MMPC_RESUME_GRID) : grid), dim3(MMPC_WAVE), h->lds_bytes, st,
+                           h->dp, B, a.x_init, a.traj, a.uref, a.ulast, a.xguess, a.obs, a.X, a.U, a.s, a.status, a.iters, a.cost, a.err,
+                           resume ? h->d_list : order, h->d_soc, h->soc_doubles, h->d_tick, h->scale_max_grad, h->d_scale_out,
+                           resume ? (const int *)nullptr : ucount, resume ? 0 : h->budget, h->d_state, h->state_doubles,
+                           resume ? h->d_count : (const int *)nullptr);
     } else
         hipLaunchKernelGGL(h->gen_fn, dim3(grid), dim3(MMPC_WAVE), h->gen_dyn_lds, st, h->dp, B, a.x_init, a.traj, a.uref, a.ulast,
                            a.xguess, a.obs, a.X, a.U, a.s, a.status, a.iters, a.cost, a.err, order, h->d_soc, h->soc_doubles, h->d_tick,
                            h->scale_max_grad, h->d_scale_out, ucount);
     HIPCHK(h, hipGetLastError());
-    if (use_fast && h->budget > 0 && !resume) {
+    if ((use_fast || gen_cont) && h->budget > 0 && !resume) {
         // who is suspended: compacted list for mmpc_resume_batch_device
         HIPCHK(h, hipMemsetAsync(h->d_count, 0, 4, st));
         if (ulist) hipLaunchKernelGGL(mmpc_collect_suspended_list, dim3((mode.capacity + 255) / 256), dim3(256), 0, st, B, ulist, ucount, a.status, h->d_list, h->d_count);
         else hipLaunchKernelGGL(mmpc_collect_suspended, dim3((B + 255) / 256), dim3(256), 0, st, B, a.status, h->d_list, h->d_count);
         h->resume_B = B;
+        h->resume_fast = use_fast ? 1 : 0;
     }
     if (lpt && h->hint_on == 1) {
         hipLaunchKernelGGL(mmpc_lpt_order, dim3(1), dim3(MMPC_LPT_THREADS), 0, st, B, a.iters, h->d_order);
@@ -695,7 +767,7 @@ static int launch_device(mmpc_handle h, int B, MmpcBatch a, void *stream, const 
 
 extern "C" int mmpc_set_iteration_budget(mmpc_handle h, int budget) {
     if (!h || budget < 0) return fail(h, MMPC_E_ARG, "mmpc_set_iteration_budget: %s%s", "budget must be >= 0");
-    if (budget > 0 && !h->fast_fn[0]) return fail(h, MMPC_E_UNSUPPORTED, "mmpc_set_iteration_budget: %s%s", "this (kind, N, M) runs the generic kernel, which has no continuation");
+    if (budget > 0 && !h->fast_fn[0] && !h->gen_cont_fn) return fail(h, MMPC_E_UNSUPPORTED, "mmpc_set_iteration_budget: %s%s", "this (kind, N, M) runs the generic kernel, which has no continuation");
     HIPCHK(h, hipSetDevice(h->cfg.device));
     if (budget > 0 && !h->d_state) {
         const size_t B = (size_t)h->cfg.max_batch;
@@ -799,7 +871,7 @@ extern "C" int mmpc_solve_rows_device(mmpc_handle h, int B, const int *d_list, c
     const MmpcBatch a = {d_x_init, d_traj_ref, d_u_ref, d_u_last, d_x_guess, d_obs, d_X, d_U, d_s, d_status, d_iters, d_cost, d_err};
     if (bad_batch(h, B, a) || !d_list || !d_count || capacity < 1 || capacity > B)
         return fail(h, MMPC_E_ARG, "mmpc_solve_rows_device: %s%s", "bad argument (B in 1..max_batch, 1 <= capacity <= B)");
-    if (h->budget > 0)
+    if (h->budget > 0 && !h->gen_cont_fn)
         return fail(h, MMPC_E_UNSUPPORTED, "mmpc_solve_rows_device: %s%s", "the handle has an iteration budget set (continuations belong to mmpc_solve_list_device)");
     return launch_device(h, B, a, stream, MmpcMode{MMPC_LIST, d_list, d_count, capacity, true});
 }
@@ -831,7 +903,7 @@ extern "C" int mmpc_solve_batch(mmpc_handle h, int B, const double *x_init, cons
                          h->d_status, h->d_iters, h->d_cost, h->d_err};
     int rc = launch(h, B, a, st, whole_batch);
     if (rc) return rc;
-    if (h->budget > 0 && h->fast_fn[0] && h->d_state) {   // the host-pointer call returns finished solves: continue the suspended ones at once
+    if (h->budget > 0 && (h->fast_fn[0] || h->gen_cont_fn) && h->d_state) {   // the host-pointer call returns finished solves: continue the suspended ones at once
         rc = launch(h, B, a, st, continuation);
         if (rc && rc != MMPC_E_UNSUPPORTED) return rc;
     }

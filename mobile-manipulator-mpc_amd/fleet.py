@@ -49,16 +49,23 @@ tick is unchanged (U_last stays the previous optimum).  It is a keyword of run_m
 specialise=False / "cached" / True: every handle of the fleet (sub-fleets of run_groups and the handles of run_async included) is
 created with this value (_capi.prepare_shape): an unlisted (N, M) then runs the specialised kernels of its shape library - which
 also gives it iteration budgets, and with them run_async.  True builds a missing library first: one to two minutes of hipcc.
+
+generic_budget=True: every handle of the fleet (sub-fleets of run_groups, the handles of run_async and the mission handles included)
+is created with mmpc_config.generic_budget: iteration budgets and continuation also where a handle runs the generic kernel.  run_async
+then works at an unlisted (N, M) without a shape library - no hipcc run -, with the per-robot results of run_lockstep bit for bit.  The
+handles run the run-time-sized generic kernel (not the static-LDS instantiation of a listed configuration).  Missions are not part of
+run_async: run_mission sets no budget.
 """
 import numpy as np
 
 
 class DeviceFleet:
     def __init__(self, mm, x0, glob, obs0, vel, N=30, device=0, dt=0.1, handles=3, fused=False, warm_start="reference", obstacles="table",
-                 nlp_scaling=None, nlp_scaling_max_gradient=100.0, specialise=False):
+                 nlp_scaling=None, nlp_scaling_max_gradient=100.0, specialise=False, generic_budget=False):
         import torch
         self.nlp_scaling, self.nlp_scaling_max_gradient = nlp_scaling, nlp_scaling_max_gradient
         self.specialise = specialise
+        self.generic_budget = bool(generic_budget)
         if obstacles not in ("table", "motion"):
             raise ValueError("obstacles must be 'table' or 'motion', not %r" % (obstacles,))
         self.obstacles = obstacles
@@ -74,7 +81,8 @@ class DeviceFleet:
         B, M = self.B, self.M
         mk = lambda: mm.MPCWholeBody(mm.MobileManipulator(dt), [], [], N=N, max_batch=max(B, 1), device=device, n_obstacles=M,
                                      obs_per_stage="motion" if self.motion else True, nlp_scaling=nlp_scaling,
-                                     nlp_scaling_max_gradient=nlp_scaling_max_gradient, specialise=specialise)
+                                     nlp_scaling_max_gradient=nlp_scaling_max_gradient, specialise=specialise,
+                                     generic_budget=self.generic_budget)
         # [0]: lock step (plain kernel); [1], [2]: the two alternating handles of run_async, created on its first call.  A handle owns
         # max_batch rows of device state: staging, warm start, the second-order-correction scratch and - long horizons - the gain
         # blocks (mmpc_create: about 0.5 MB per robot at N = 30, M = 8)
@@ -403,7 +411,7 @@ class DeviceFleet:
                 sub = DeviceFleet(mm, self.x0[lo:hi], self.glob[lo:hi], self.obs0[lo:hi], self.vel[lo:hi], N=self.N, device=self.dev.index, dt=self.dt,
                                   handles=1, fused=self.fused, warm_start=self.warm_start, obstacles=self.obstacles,
                                   nlp_scaling=self.nlp_scaling, nlp_scaling_max_gradient=self.nlp_scaling_max_gradient,
-                                  specialise=self.specialise)
+                                  specialise=self.specialise, generic_budget=self.generic_budget)
                 # (priority: lower number = served first; the last group runs at the default priority)
                 pr = (max(hi_pr, min(lo_pr, 0 - (G - 1 - g))) if hi_pr < 0 else 0) if priority else 0
                 self._groups.append((lo, hi, sub, torch.cuda.Stream(device=self.dev, priority=pr)))
