@@ -242,6 +242,14 @@ int mmpc_set_objective_scaling(mmpc_handle h, double max_gradient, double *d_sca
  * Results never depend on the order.  No reference counterpart (the reference solves one instance at a time). */
 int mmpc_set_schedule_hint(mmpc_handle h, int mode);
 
+/* Grid of the plain launch of a specialised kernel (whole batch, no iteration budget).  That launch is persistent: it starts as
+ * many workgroups as the device holds at once (problems per CU x compute units, at most B), and a workgroup that has finished an
+ * instance draws the next position of the launch order from a counter of the handle - a slot never waits for the dispatch of a
+ * new workgroup.  n = 0 (default): that grid; n > 0: n workgroups (at most B; a small n makes every workgroup solve several
+ * instances in turn - tests); n < 0: one workgroup per instance, the launch form of budgeted, continuation and list launches and of
+ * the generic kernels, which this call does not change.  Results never depend on n.  Read by the handle's next launch. */
+int mmpc_set_persistent_grid(mmpc_handle h, int n);
+
 /* Iteration budget and continuation (specialised kernels; the generic kernel on a handle created with cfg.generic_budget - "either
  * family" below; no reference counterpart - IPOPT runs one instance to the end).  One wave solves one instance, so a launch lasts as long as its slowest instance: a handful of instances that need
  * several hundred iterations (heavy tail of the interior-point iteration count) would hold the results of thousands of

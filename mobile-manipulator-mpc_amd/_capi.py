@@ -29,7 +29,7 @@ EXPORTS = ["mmpc_create", "mmpc_destroy", "mmpc_set_weights", "mmpc_set_terminal
            "mmpc_lds_bytes", "mmpc_problems_per_cu", "mmpc_set_warm_start", "mmpc_set_schedule_hint", "mmpc_set_iteration_budget", "mmpc_resume_batch_device", "mmpc_solve_list_device", "mmpc_suspended_count", "mmpc_last_error", "mmpc_version", "mmpc_ik_batch", "mmpc_ik_batch_device",
            "mmpc_tick_prepare_device", "mmpc_set_obstacle_clock", "mmpc_set_objective_scaling",
            "mmpc_mission_prepare_device", "mmpc_manipulate_prepare_device", "mmpc_solve_rows_device", "mmpc_shift_guess_device",
-           "mmpc_shape_supported", "mmpc_load_shape_library", "mmpc_runs_specialised"]
+           "mmpc_shape_supported", "mmpc_load_shape_library", "mmpc_runs_specialised", "mmpc_set_persistent_grid"]
 LISTED_SHAPES = ((KIND_WHOLEBODY, 20, 5), (KIND_WHOLEBODY, 30, 8), (KIND_WHOLEBODY, 20, 3), (KIND_BASE, 15, 3))   # MMPC_FAST_LIST
 
 _lib = None
@@ -66,6 +66,7 @@ def lib():
         L.mmpc_problems_per_cu.argtypes = [C.c_void_p]
         L.mmpc_set_warm_start.argtypes = [C.c_void_p, C.c_void_p, C.c_double]
         L.mmpc_set_schedule_hint.argtypes = [C.c_void_p, C.c_int]
+        L.mmpc_set_persistent_grid.argtypes = [C.c_void_p, C.c_int]
         L.mmpc_set_iteration_budget.argtypes = [C.c_void_p, C.c_int]
         L.mmpc_resume_batch_device.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 13 + [C.c_void_p]
         L.mmpc_solve_list_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 13 + [C.c_void_p]
@@ -304,6 +305,11 @@ class Engine:
         by the previous launch's iteration counts when there is one, else by the a-priori difficulty key of the batch's own
         data, 2 always the a-priori key."""
         self._chk(lib().mmpc_set_schedule_hint(self._h, int(mode)), "mmpc_set_schedule_hint")
+
+    def set_persistent_grid(self, n):
+        """mmpc_set_persistent_grid: workgroups of the plain launch of a specialised kernel - 0 (default) what the device holds
+        at once, n > 0 that many (each solves several instances in turn), n < 0 one workgroup per instance."""
+        self._chk(lib().mmpc_set_persistent_grid(self._h, int(n)), "mmpc_set_persistent_grid")
 
     def set_iteration_budget(self, budget):
         """mmpc_set_iteration_budget: iterations a launch may spend on an instance before it is suspended (0: off).  Needs a

@@ -33,6 +33,8 @@
 //   MMPC_PIV_NEWTON             mmpc_rcp_piv with one Newton step or the cubic step of mmpc_rcp; 1; the same tests
 //   MMPC_STAMP, _STAMP_COARSE   per-phase cycle stamps of the specialised kernel (without those inside the stage loop); off; tools/probe_stamps.py
 //   MMPC_STAMP_GEN, _GEN_A, _GEN_E   the same for the generic kernel (slots 10..15: assembly / evaluation pieces); off; tools/probe_stamps_generic.py
+//   MMPC_STAMP_INST             per-instance start / end stamps, XCD and workgroup of the specialised kernels (mmpc_fast_kernel.h); off;
+//                               tools/persistent_launch_probe.py --stamps
 //   MMPC_PHASE_SYNC             __syncthreads() at every phase end instead of the wavefront-scope fence; off; tools/sync_check.py
 //   MMPC_FAST_LIST, MMPC_STATIC_LIST   the instantiation lists of mmpc_hip.hip; the full lists; tools/build_variant.sh, tools/occupancy_probe.sh
 //   MMPC_SLIM_NMIN 21, MMPC_GAINS_GLOBAL_NMIN, MMPC_RG_NMIN (both MMPC_SLIM_NMIN), MMPC_RG_MAX 3, MMPC_UNROLL_NMAX 30, MMPC_RIC_UNROLL 2,

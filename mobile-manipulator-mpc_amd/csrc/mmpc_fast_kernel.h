@@ -5,6 +5,24 @@
 #pragma once
 #include "mmpc_fast.h"
 
+// Diagnostic build only (-DMMPC_STAMP_INST, tools/persistent_launch_probe.py --stamps): per instance row the start and the end of its
+// solve on the 100 MHz clock all XCDs share and on the wave's cycle counter, the XCD and the workgroup that solved it.  The shipped
+// kernels contain no stamps.
+#ifdef MMPC_STAMP_INST
+#define MMPC_INST_STAMP_ROWS 8192
+__device__ unsigned long long mmpc_inst_stamp[6 * MMPC_INST_STAMP_ROWS];
+#define MMPC_INST_T0() const unsigned long long ir0_ = __builtin_amdgcn_s_memrealtime(), ic0_ = __builtin_readcyclecounter();
+#define MMPC_INST_T1(b)                                                                                                        \
+    if (threadIdx.x == 0 && (b) < MMPC_INST_STAMP_ROWS) {                                                                      \
+        unsigned long long *q_ = mmpc_inst_stamp + 6 * (b);                                                                    \
+        q_[0] = ir0_; q_[1] = __builtin_amdgcn_s_memrealtime(); q_[2] = ic0_; q_[3] = __builtin_readcyclecounter();             \
+        q_[4] = __builtin_amdgcn_s_getreg(20 | (3 << 11)); q_[5] = blockIdx.x;   /* (HW_REG_XCC_ID, bits 3:0) */                 \
+    }
+#else
+#define MMPC_INST_T0()
+#define MMPC_INST_T1(b)
+#endif
+
 // OPS = the config's obs_per_stage (0 static record, 1 table per stage, 2 motion record + clock): part of the LDS layout.  The LDS block is STATIC (its size is a
 // constant of the instantiation): with `extern __shared__` the base of the dynamic block is resolved after instruction
 // selection and every lane-derived LDS address carries an add of that constant 0 (14 of the ~200 instructions of a Riccati stage).
@@ -16,7 +34,7 @@ __global__ __launch_bounds__(MMPC_WAVE, WPE) void mmpc_fast_kernel(
     int *__restrict__ status, int *__restrict__ iters, double *__restrict__ cost, double *__restrict__ err,
     const int *__restrict__ order, int budget, double *__restrict__ state, int state_stride, const int *__restrict__ resume_count,
     const int *__restrict__ list_count, double *__restrict__ gscr, double *__restrict__ soc, int soc_stride,
-    const long long *__restrict__ tick, double scale_max_grad, double *__restrict__ scale_out) {
+    const long long *__restrict__ tick, double scale_max_grad, double *__restrict__ scale_out, int *__restrict__ ticket) {
     __shared__ double lds[mmpc_fast_layout<KIND, N>(MC, OPS).total];
     // A continuation launch (resume_count != null): `order` is the compacted list of the suspended instances, *resume_count its
     // length, and the grid is SMALL (MMPC_RESUME_GRID workgroups that stride over the list): a handful of instances is left,
@@ -25,12 +43,25 @@ __global__ __launch_bounds__(MMPC_WAVE, WPE) void mmpc_fast_kernel(
     // A list launch (list_count != null, mmpc_solve_list_device): `order` is the caller's list of instances, *list_count its length
     // (read on the device: the caller need not know it), the grid is the list's capacity.
     const int limit = resume_count ? *resume_count : (list_count ? *list_count : B);
-    for (int w = (int)blockIdx.x; w < limit; w += (int)gridDim.x) {
-        // launch order: workgroup i solves instance order[i] (a permutation / a list; results do not depend on it)
+    // A persistent launch (ticket != null; the plain launch of the kernels without the continuation code, mmpc_set_persistent_grid): the
+    // grid is what the chip holds at once, and a workgroup that has finished an instance draws the next launch position from *ticket
+    // - a greedy queue in launch order, without the dispatch of a new workgroup (its LDS allocation, its wave launch) at every
+    // turnover of a slot.  *ticket is 0 when the kernel starts and 0 again when it ends: the tickets drawn are 0 .. B + grid - 1,
+    // each once, every workgroup draws exactly one that is >= B, and the one that draws the last has seen every other draw - it
+    // puts the counter back, so no launch needs a memset or another kernel before it.
+    const bool pers = !CONT && ticket != nullptr;
+    auto take = [&]() -> int {
+        int t = 0;
+        if (threadIdx.x == 0) t = atomicAdd(ticket, 1);
+        return __builtin_amdgcn_readfirstlane(t);
+    };
+    int w = pers ? take() : (int)blockIdx.x;
+    for (; w < limit; w = pers ? take() : w + (int)gridDim.x) {
+        // launch order: position w solves instance order[w] (a permutation / a list; results do not depend on it)
         const int b = order ? order[w] : w;
         // (a list launch takes its row indices from the caller's device memory, where nothing can have checked them: an index
         //  outside the batch is skipped - it would address the inputs, the outputs and the handle's own save areas)
-        if ((unsigned)b >= (unsigned)B) { if (!CONT || !resume_count) break; continue; }
+        if ((unsigned)b >= (unsigned)B) { if (!pers && (!CONT || !resume_count)) break; continue; }
         const MmpcParams &P = *Pp;
         const int M = MC;
         const size_t so = OPS == 2 ? (size_t)M * 5 : (size_t)(P.obs_per_stage ? N + 1 : 1) * M * 3;
@@ -43,16 +74,19 @@ __global__ __launch_bounds__(MMPC_WAVE, WPE) void mmpc_fast_kernel(
         io.gscr = MmpcGainBlock<KIND, N>::ON ? gscr + (size_t)b * MmpcGainBlock<KIND, N>::total : nullptr;
         if (OPS == 2 && tick) io.tick = tick + b;   // the clock is indexed by instance row, like every per-instance array
         io.scale_max_grad = scale_max_grad; if (scale_out) io.scale_out = scale_out + b;   // (objective scaling; by instance row too)
+        MMPC_INST_T0()
         mmpc_solve_fast<KIND, N, MC, CONT, OPS>(P, io, lds);
-        if (!CONT || !resume_count) break;      // (one instance per workgroup except in a continuation launch)
+        MMPC_INST_T1(b)
+        if (!pers && (!CONT || !resume_count)) break;      // (one instance per workgroup except in a continuation or a persistent launch)
         __builtin_amdgcn_s_barrier();           // the next instance reuses the LDS block
     }
+    if (pers && w == limit + (int)gridDim.x - 1 && threadIdx.x == 0) atomicExch(ticket, 0);
 }
 
 // the signature of mmpc_fast_kernel<>
 typedef void (*mmpc_fast_fn)(const MmpcParams *, int, const double *, const double *, const double *, const double *, const double *,
                              const double *, double *, double *, double *, int *, int *, double *, double *, const int *, int, double *,
-                             int, const int *, const int *, double *, double *, int, const long long *, double, double *);
+                             int, const int *, const int *, double *, double *, int, const long long *, double, double *, int *);
 
 // Contents of the kernel sources as build.py hashes them (-DMMPC_SOURCE_TAG=0x...ULL, the same value for libmmpc.so and for every
 // shape library): MmpcParams and the kernel argument list are no stable ABI, so a library from other sources is refused.

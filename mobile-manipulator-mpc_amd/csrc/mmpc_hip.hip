@@ -318,6 +318,10 @@ struct mmpc_handle_s {
     int *d_status, *d_iters;
     int *d_order;           // LPT schedule hint from the previous launch (valid for order_B instances)
     int order_B;
+    // persistent plain launch of the specialised kernels (mmpc_set_persistent_grid; the kernel: mmpc_fast_kernel.h)
+    int persistent_grid;    // 0: automatic (fast_per_cu x n_cu workgroups), > 0: that many, < 0: one workgroup per instance
+    int n_cu;               // compute units of the handle's device
+    int *d_ticket;          // the launch-position counter the workgroups draw from: 0 between launches (the kernel puts it back)
     char err[512];
 };
 
@@ -393,6 +397,14 @@ extern "C" int mmpc_debug_read_gstamps(unsigned long long *out16) {
     unsigned long long z[16] = {0};
     if (hipMemcpyToSymbol(HIP_SYMBOL(mmpc_gstamp_acc), z, sizeof(z)) != hipSuccess) return -1;
     return 0;
+}
+#endif
+#ifdef MMPC_STAMP_INST
+// diagnostic build only: the per-instance stamps of the last launch of a specialised kernel, rows 0 .. n - 1 (not part of include/mmpc.h)
+extern "C" int mmpc_debug_read_inst_stamps(unsigned long long *out, int n) {
+    if (!out || n < 0 || n > MMPC_INST_STAMP_ROWS) return -1;
+    if (hipDeviceSynchronize() != hipSuccess) return -1;
+    return hipMemcpyFromSymbol(out, HIP_SYMBOL(mmpc_inst_stamp), (size_t)n * 6 * sizeof(unsigned long long)) == hipSuccess ? 0 : -1;
 }
 #endif
 extern "C" const char *mmpc_version(void) { return "mmpc 0.1 (gfx950)"; }
@@ -597,6 +609,9 @@ extern "C" int mmpc_create(const mmpc_config *cfg, mmpc_handle *out) {
     HIPCHK(h, hipMalloc(&h->d_order, B * 4));
     HIPCHK(h, hipMalloc(&h->d_warm, B * 4));
     HIPCHK(h, hipMalloc(&h->d_key, B * 4));
+    HIPCHK(h, hipMalloc(&h->d_ticket, 4));
+    HIPCHK(h, hipMemset(h->d_ticket, 0, 4));
+    HIPCHK(h, hipDeviceGetAttribute(&h->n_cu, hipDeviceAttributeMultiprocessorCount, cfg->device));
     if (h->fast_fn[0] && h->gscr_doubles) HIPCHK(h, hipMalloc(&h->d_gscr, B * (size_t)h->gscr_doubles * 8));
     h->soc_doubles = mmpc_soc_doubles(cfg->N, h->nx, h->nu, L.NR);
     HIPCHK(h, hipMalloc(&h->d_soc, B * (size_t)h->soc_doubles * 8));
@@ -619,7 +634,7 @@ extern "C" int mmpc_destroy(mmpc_handle h) {
     if (!h) return MMPC_E_ARG;
     void *ptrs[] = {h->dp, h->d_x_init, h->d_traj, h->d_uref, h->d_obs, h->d_ulatest, h->d_xguess, h->d_X, h->d_U,
                     h->d_s, h->d_cost, h->d_err, h->d_u0, h->d_status, h->d_iters, h->d_order, h->d_warm, h->d_key, h->d_state,
-                    h->d_list, h->d_count, h->d_gscr, h->d_soc};
+                    h->d_list, h->d_count, h->d_gscr, h->d_soc, h->d_ticket};
     (void)hipSetDevice(h->cfg.device);
     if (h->ev_valid) (void)hipEventSynchronize(h->ev);
     if (h->ev) (void)hipEventDestroy(h->ev);
@@ -719,12 +734,20 @@ static int launch(mmpc_handle h, int B, const MmpcBatch &a, hipStream_t st, cons
     if (use_fast) {
         // CONT instantiation: the launch may suspend (a budget is set) or continues suspended instances; only it gets the save areas
         const bool cont = resume || h->budget > 0;
-        hipLaunchKernelGGL(h->fast_fn[cont], dim3(resume ? (B < MMPC_RESUME_GRID ? B : MMPC_RESUME_GRID) : grid), dim3(MMPC_WAVE), 0, st,
+        // the plain launch (whole batch, no budget) is persistent: as many workgroups as the chip holds at once, which draw their
+        // launch positions from the handle's ticket (mmpc_set_persistent_grid)
+        const bool pers = !cont && !ulist && h->persistent_grid >= 0 && h->fast_per_cu > 0 && h->n_cu > 0;
+        int pgrid = grid;
+        if (pers) {
+            const long long room = h->persistent_grid > 0 ? (long long)h->persistent_grid : (long long)h->fast_per_cu * h->n_cu;
+            pgrid = room < B ? (int)room : B;
+        }
+        hipLaunchKernelGGL(h->fast_fn[cont], dim3(resume ? (B < MMPC_RESUME_GRID ? B : MMPC_RESUME_GRID) : pgrid), dim3(MMPC_WAVE), 0, st,
                            h->dp, B, a.x_init, a.traj, a.uref, a.ulast, a.xguess, a.obs, a.X, a.U, a.s, a.status, a.iters, a.cost, a.err,
                            resume ? h->d_list : order, resume ? 0 : h->budget, cont ? h->d_state : (double *)nullptr,
                            cont ? h->state_doubles : 0, resume ? h->d_count : (const int *)nullptr,
                            resume ? (const int *)nullptr : ucount, h->d_gscr, h->d_soc, h->soc_doubles, h->d_tick,
-                           h->scale_max_grad, h->d_scale_out);
+                           h->scale_max_grad, h->d_scale_out, pers ? h->d_ticket : (int *)nullptr);
     } else if (gen_cont && (resume || h->budget > 0)) {
         hipLaunchKernelGGL(h->gen_cont_fn, dim3(resume ? (B < MMPC_RESUME_GRID ? B : MMPC_RESUME_GRID) : grid), dim3(MMPC_WAVE), h->lds_bytes, st,
                            h->dp, B, a.x_init, a.traj, a.uref, a.ulast, a.xguess, a.obs, a.X, a.U, a.s, a.status, a.iters, a.cost, a.err,
@@ -808,6 +831,12 @@ extern "C" int mmpc_set_schedule_hint(mmpc_handle h, int on) {
     if (on < 0 || on > 2) return fail(h, MMPC_E_ARG, "mmpc_set_schedule_hint: %s%s", "mode must be 0, 1 or 2");
     h->hint_on = on;
     h->order_B = 0;
+    return MMPC_OK;
+}
+
+extern "C" int mmpc_set_persistent_grid(mmpc_handle h, int n) {
+    if (!h) return MMPC_E_ARG;
+    h->persistent_grid = n;   // (read by the next launch; launches in flight have their grid already)
     return MMPC_OK;
 }
 
