@@ -928,6 +928,7 @@ MMPC_DEV void mmpc_solve_one(const MmpcParams &P, const MmpcIO io, double *lds M
     constexpr bool PAIRS = GR::PAIRS;
 #ifdef MMPC_EMU
     static thread_local GR ls_all[MMPC_WAVE];
+    MMPC_EMU_LANE_HOOK(ls_all, sizeof(ls_all))
 #else
     GR ls_one;
 #endif

@@ -489,7 +489,9 @@ MMPC_DEV void mmpc_solve_fast(const MmpcParams &P, const MmpcIO io, double *lds 
     double Sw = P.S;   // (objective scaling: P.S times the factor of the objective)
 #ifdef MMPC_EMU
     static thread_local MmpcLaneState<KIND, N, MC> ls_all[MMPC_WAVE];
+    MMPC_EMU_LANE_HOOK(ls_all, sizeof(ls_all))
     static thread_local double wr_all[MMPC_WAVE][9];
+    MMPC_EMU_LANE_HOOK(wr_all, sizeof(wr_all))
 #else
     MmpcLaneState<KIND, N, MC> ls_one;
     double wr_one[9];

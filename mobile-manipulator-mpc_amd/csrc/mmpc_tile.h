@@ -16,6 +16,10 @@
 #define MMPC_WAVE_ANY(x) (x)     // (a flag declared outside the lane loop has been or-ed / min-ed over the lanes by the loop itself)
 #define MMPC_FW_SLOT(k) ((k) & 1)
 #define LANES_END_REG }
+// the lane state of this build is static: a test harness may define this to overwrite it at the entry of a solve (nothing otherwise)
+#ifndef MMPC_EMU_LANE_HOOK
+#define MMPC_EMU_LANE_HOOK(ptr, bytes)
+#endif
 #else
 #define MMPC_LS ls_one
 #define MMPC_WR(i) wr_one[i]

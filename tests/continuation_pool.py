@@ -212,6 +212,27 @@ def uninterrupted(name):
     return _ref[name]
 
 
+def warm(name, u_guess, x_guess, mu_init):
+    """the case's solve in one launch on its host build from a warm start (mmpc_set_warm_start + the X guess of the launch): U
+    guess (B, N, nu), X guess (B, N+1, nx), initial barrier parameter"""
+    c = case(name)
+    par, d, (k, N, M) = c["par"], c["d"], c["shape"]
+    u_guess, x_guess = np.ascontiguousarray(u_guess, float), np.ascontiguousarray(x_guess, float)
+    assert u_guess.shape == d["u_last"].shape and x_guess.shape == d["traj_ref"].shape
+    if c["backend"] == "emu":
+        return emu_helper.solve_batch(par, d["x_init"], d["traj_ref"], d["u_ref"], d["u_last"], d["obs"], x_guess=x_guess, u_guess=u_guess,
+                                      fast=True, mu_init=mu_init, max_iter=MAX_ITER)
+    r = HostRun(c)
+    r.prm.mu_init, r.prm.u_guess = float(mu_init), u_guess.ctypes.data
+    fn = C.CDLL(motion_helper.build()).mmpc_emum_solve_fast_guess if c["backend"] == "motion" else shape_helper.lib(c["shape"]).mmpc_emush_solve_fast_guess
+    o = r.out
+    tp = r.tick.ctypes.data_as(C.POINTER(C.c_longlong)) if r.tick is not None else None
+    rc = fn(k, C.byref(r.prm), r.B, _p(d["x_init"]), _p(d["traj_ref"]), _p(d["u_ref"]), _p(d["u_last"]), _p(d["obs"]), tp, _p(o["X"]), _p(o["U"]),
+            _p(o["s"]), _i(o["status"]), _i(o["iters"]), _p(o["cost"]), _p(o["err"]), 0, 0, None, 0, _p(x_guess))
+    assert rc == 0
+    return r.snapshot()
+
+
 def chain(name):
     """the case cut at every iteration on its host build: (outputs, scal[l, b, :] = emu_helper.SCALARS parked after launch l - NaN
     where instance b was not suspended -, launches, areas[l] = the save areas after launch l); once per case"""

@@ -5,6 +5,7 @@
 // against the oracle before anything is launched on a GPU.  `reverse` runs the lanes of every
 // phase in the opposite order: a result that changes exposes an intra-phase data race.
 #define MMPC_EMU 1
+#include "../emu_common/mmpc_emu_poison.h"
 #include "../../mobile-manipulator-mpc_amd/csrc/mmpc_fast.h"
 #include "../../mobile-manipulator-mpc_amd/csrc/mmpc_ik.h"
 #include <stdlib.h>
@@ -19,22 +20,18 @@ static void run(const MmpcParams *P, int B, const double *x_init, const double *
     MmpcLayout L = mmpc_layout<KIND>(N, M, P->obs_per_stage, (KIND == 0 && P->L > 0) ? 6 : 0,
                                      (KIND == 0 && P->L >= 2 && P->as_written) ? 6 * (P->L - 1) : 0);
     const size_t so = (size_t)(P->obs_per_stage ? N + 1 : 1) * M * 3;
+    MmpcEmuBlock lds_b, soc_b;   // (mmpc_emu_poison.h: what the blocks hold at the start of an instance is the caller's choice, NaN by default)
     for (int b = 0; b < B; b++) {
         // exact-size heap slab so that ASAN sees any out-of-slab access
-        double *lds = (double *)malloc(sizeof(double) * L.total);
-        for (int i = 0; i < L.total; i++) lds[i] = NAN;
+        double *lds = lds_b.next(L.total);
         // scratch of the second-order correction (global memory on the device), exact size as the slab
-        const int sdn = mmpc_soc_doubles(N, D::NX, D::NU, L.NR);
-        double *soc = (double *)malloc(sizeof(double) * sdn);
-        for (int i = 0; i < sdn; i++) soc[i] = NAN;
+        double *soc = soc_b.next(mmpc_soc_doubles(N, D::NX, D::NU, L.NR));
         // (the scratch is this instance's own: stride 0)
         MmpcIO io;
         mmpc_instance_io<KIND>(io, *P, b, N, so, x_init, traj_ref, u_ref, u_last, x_guess, obs, X, U, s, status, iters, cost, err,
                                soc, 0);
         MmpcEmu emu = reverse ? MmpcEmu{63, -1, -1} : MmpcEmu{0, 64, 1};
         mmpc_solve_one<KIND>(*P, io, lds, emu);
-        free(soc);
-        free(lds);
     }
 }
 
@@ -47,26 +44,20 @@ static void run_fast(const MmpcParams *P, int B, const double *x_init, const dou
     const int M = MC;
     MmpcFastLayout L = mmpc_fast_layout<KIND, N>(M, P->obs_per_stage);
     const size_t so = (size_t)(P->obs_per_stage ? N + 1 : 1) * M * 3;
+    MmpcEmuBlock lds_b, gscr_b, soc_b;
     for (int b = 0; b < B; b++) {
-        double *lds = (double *)malloc(sizeof(double) * L.total);
-        for (int i = 0; i < L.total; i++) lds[i] = NAN;
         const int sd = mmpc_fast_state_doubles<KIND, N>(MC);
-        if (resume && status[b] != 3) { free(lds); continue; }   // a continuation launch only runs the suspended instances
+        if (resume && status[b] != 3) continue;   // a continuation launch only runs the suspended instances
+        double *lds = lds_b.next(L.total);
         MmpcEmu emu = reverse ? MmpcEmu{63, -1, -1} : MmpcEmu{0, 64, 1};
         // gain block of the long horizons (global memory on the device)
-        const int gd = MmpcGainBlock<KIND, N>::total;
-        double *gscr = gd ? (double *)malloc(sizeof(double) * gd) : nullptr;
-        for (int i = 0; i < gd; i++) gscr[i] = NAN;
-        const int sdn = mmpc_soc_doubles(N, D::NX, D::NU, MC + D::NSELF);
-        double *soc = (double *)malloc(sizeof(double) * sdn);
-        for (int i = 0; i < sdn; i++) soc[i] = NAN;
+        double *gscr = gscr_b.next(MmpcGainBlock<KIND, N>::total);
+        double *soc = soc_b.next(mmpc_soc_doubles(N, D::NX, D::NU, MC + D::NSELF));
         MmpcIO io;
         mmpc_instance_io<KIND>(io, *P, b, N, so, x_init, traj_ref, u_ref, u_last, x_guess, obs, X, U, s, status, iters, cost, err,
                                soc, 0);
         io.state = state ? state + (size_t)b * sd : nullptr; io.budget = budget; io.resume = resume; io.gscr = gscr;   // (as mmpc_fast_kernel)
         if (budget > 0 || resume) mmpc_solve_fast<KIND, N, MC, true>(*P, io, lds, emu); else mmpc_solve_fast<KIND, N, MC, false>(*P, io, lds, emu);
-        free(gscr); free(soc);
-        free(lds);
     }
 }
 

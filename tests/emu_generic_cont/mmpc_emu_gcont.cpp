@@ -4,6 +4,7 @@
 // tests/test_generic_continuation_cpu.py through tests/generic_cont_helper.py.  -DMMPC_EMUG_MAIN adds a main() that cuts one small
 // batch at every iteration, so that the same code can be built as a stand-alone program under a sanitizer.
 #define MMPC_EMU 1
+#include "../emu_common/mmpc_emu_poison.h"
 #include "../../mobile-manipulator-mpc_amd/csrc/mmpc_core.h"
 #include <stdlib.h>
 #include <string.h>
@@ -15,8 +16,9 @@ static MmpcLayout layout_of(const MmpcParams *P) {
 }
 
 // cont: the CONT = true instantiation (budget, state, resume as the kernel wrapper sets them); a continuation launch (resume != 0)
-// runs the instances whose status[] is 3 and leaves the others alone.  Slab, correction scratch: exact-size heap blocks filled with
-// NaN, as tests/emu/mmpc_emu.cpp - a continuation that reads a word it has not restored or recomputed reads a NaN.
+// runs the instances whose status[] is 3 and leaves the others alone.  Slab, correction scratch: exact-size heap blocks filled as
+// mmpc_emu_poison.h says (NaN by default), as tests/emu/mmpc_emu.cpp - a continuation that reads a word it has not restored or
+// recomputed reads what the test put there.
 template <int KIND>
 static void run(const MmpcParams *P, int B, const double *x_init, const double *traj_ref, const double *u_ref, const double *u_last,
                 const double *x_guess, const double *obs, const long long *tick, double *X, double *U, double *s, int *status, int *iters,
@@ -26,13 +28,11 @@ static void run(const MmpcParams *P, int B, const double *x_init, const double *
     const MmpcLayout L = layout_of<KIND>(P);
     const int sd = mmpc_gen_state(D::NX, D::NU, N, L.R).total;
     const size_t so = P->obs_per_stage == 2 ? (size_t)M * 5 : (size_t)(P->obs_per_stage ? N + 1 : 1) * M * 3;
+    MmpcEmuBlock lds_b, soc_b;
     for (int b = 0; b < B; b++) {
         if (resume && status[b] != 3) continue;
-        double *lds = (double *)malloc(sizeof(double) * L.total);
-        for (int i = 0; i < L.total; i++) lds[i] = NAN;
-        const int sdn = mmpc_soc_doubles(N, D::NX, D::NU, L.NR);
-        double *soc = (double *)malloc(sizeof(double) * sdn);
-        for (int i = 0; i < sdn; i++) soc[i] = NAN;
+        double *lds = lds_b.next(L.total);
+        double *soc = soc_b.next(mmpc_soc_doubles(N, D::NX, D::NU, L.NR));
         MmpcIO io;
         mmpc_instance_io<KIND>(io, *P, b, N, so, x_init, traj_ref, u_ref, u_last, x_guess, obs, X, U, s, status, iters, cost, err, soc, 0);
         if (P->obs_per_stage == 2 && tick) io.tick = tick + b;
@@ -43,8 +43,6 @@ static void run(const MmpcParams *P, int B, const double *x_init, const double *
             mmpc_solve_one<KIND, 0, -1, -1, -1, -1, true>(*P, io, lds, emu);
         } else
             mmpc_solve_one<KIND>(*P, io, lds, emu);
-        free(soc);
-        free(lds);
     }
 }
 
@@ -99,8 +97,8 @@ int main() {
     int lay[11];
     mmpc_emug_state_layout(0, &P, lay);
     const int sd = lay[10];
-    double *state = (double *)malloc(sizeof(double) * sd * B);
-    for (int i = 0; i < sd * B; i++) state[i] = NAN;
+    MmpcEmuBlock state_b;
+    double *state = state_b.next((size_t)sd * B);
     static double X[2][B][N + 1][9], U[2][B][N][5], s[2][B][N + 1], cost[2][B], err[2][B];
     static int status[2][B], iters[2][B];
 #define MMPC_EMUG_OUT(v) &X[v][0][0][0], &U[v][0][0][0], &s[v][0][0], status[v], iters[v], cost[v], err[v]
@@ -119,7 +117,6 @@ int main() {
                       !memcmp(status[0], status[1], sizeof(status[0])) && !memcmp(iters[0], iters[1], sizeof(iters[0]));
     printf("launches %d, iterations %d %d %d %d, status %d %d %d %d: %s\n", launches, iters[0][0], iters[0][1], iters[0][2], iters[0][3],
            status[0][0], status[0][1], status[0][2], status[0][3], same ? "bitwise equal" : "DIFFERENT");
-    free(state);
     return same ? 0 : 1;
 }
 #endif

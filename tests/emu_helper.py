@@ -12,6 +12,7 @@ _FAST = os.path.join(_HERE, "..", "mobile-manipulator-mpc_amd", "csrc", "mmpc_fa
 _TILE = os.path.join(_HERE, "..", "mobile-manipulator-mpc_amd", "csrc", "mmpc_tile.h")
 _IK = os.path.join(_HERE, "..", "mobile-manipulator-mpc_amd", "csrc", "mmpc_ik.h")
 _PRIM = os.path.join(_HERE, "gpu_prim", "mmpc_prim_ops.h")
+POISON_H = os.path.join(_HERE, "emu_common", "mmpc_emu_poison.h")      # what a solve starts on: shared by every host build
 
 
 class MmpcParams(C.Structure):
@@ -29,7 +30,7 @@ def build(asan=False, defs=()):
     tag = ("_" + "_".join(d.replace("=", "") for d in defs)) if defs else ""
     out = os.path.join(_HERE, "emu", "_build", ("libmmpc_emu_asan%s.so" if asan else "libmmpc_emu%s.so") % tag)
     csrc = os.path.dirname(_FAST)
-    newest = max(os.path.getmtime(f) for f in [_SRC, _CORE, _FAST, _TILE, _IK, _PRIM] + [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith('.inc')])
+    newest = max(os.path.getmtime(f) for f in [_SRC, _CORE, _FAST, _TILE, _IK, _PRIM, POISON_H] + [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith('.inc')])
     if not os.path.exists(out) or os.path.getmtime(out) < newest:
         os.makedirs(os.path.dirname(out), exist_ok=True)
         flags = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-omit-frame-pointer"] if asan else ["-O2"]

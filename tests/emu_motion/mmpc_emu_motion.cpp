@@ -5,6 +5,7 @@
 // device kernel wrappers set it.  The same entry points run modes 0 and 1 (tick unused), so one library solves a motion
 // input and its table twin.  Build with -ffp-contract=off: the centres are defined operation by operation.
 #define MMPC_EMU 1
+#include "../emu_common/mmpc_emu_poison.h"
 #include "../../mobile-manipulator-mpc_amd/csrc/mmpc_fast.h"
 #include <stdlib.h>
 #include <string.h>
@@ -27,12 +28,10 @@ static void run(const MmpcParams *P, int B, const double *x_init, const double *
     const int N = P->N, M = P->M;
     const MmpcLayout L = mmpc_layout<KIND>(N, M, P->obs_per_stage);
     const size_t so = obs_stride(P, N, M);
+    MmpcEmuBlock lds_b, soc_b;   // (mmpc_emu_poison.h: what the blocks hold at the start of an instance is the caller's choice, NaN by default)
     for (int b = 0; b < B; b++) {
-        double *lds = (double *)malloc(sizeof(double) * L.total);
-        for (int i = 0; i < L.total; i++) lds[i] = NAN;
-        const int sdn = mmpc_soc_doubles(N, D::NX, D::NU, L.NR);
-        double *soc = (double *)malloc(sizeof(double) * sdn);
-        for (int i = 0; i < sdn; i++) soc[i] = NAN;
+        double *lds = lds_b.next(L.total);
+        double *soc = soc_b.next(mmpc_soc_doubles(N, D::NX, D::NU, L.NR));
         double *ob = obs_copy(obs, b, so);
         MmpcIO io;
         mmpc_instance_io<KIND>(io, *P, b, N, so, x_init, traj_ref, u_ref, u_last, nullptr, obs, X, U, s, status, iters, cost, err, soc, 0);
@@ -40,37 +39,33 @@ static void run(const MmpcParams *P, int B, const double *x_init, const double *
         if (P->obs_per_stage == 2 && tick) io.tick = tick + b;
         MmpcEmu emu = reverse ? MmpcEmu{63, -1, -1} : MmpcEmu{0, 64, 1};
         mmpc_solve_one<KIND>(*P, io, lds, emu);
-        free(ob); free(soc); free(lds);
+        free(ob);
     }
 }
 
 template <int KIND, int N, int MC>
 static void run_fast(const MmpcParams *P, int B, const double *x_init, const double *traj_ref, const double *u_ref, const double *u_last,
                      const double *obs, const long long *tick, double *X, double *U, double *s, int *status, int *iters, double *cost,
-                     double *err, int reverse, int budget, double *state, int resume) {
+                     double *err, int reverse, int budget, double *state, int resume, const double *x_guess = nullptr) {
     typedef MmpcDims<KIND> D;
     const MmpcFastLayout L = mmpc_fast_layout<KIND, N>(MC, P->obs_per_stage);
     const size_t so = obs_stride(P, N, MC);
     const int sd = mmpc_fast_state_doubles<KIND, N>(MC);
+    MmpcEmuBlock lds_b, gscr_b, soc_b;
     for (int b = 0; b < B; b++) {
         if (resume && status[b] != 3) continue;   // a continuation launch only runs the suspended instances
-        double *lds = (double *)malloc(sizeof(double) * L.total);
-        for (int i = 0; i < L.total; i++) lds[i] = NAN;
-        const int gd = MmpcGainBlock<KIND, N>::total;
-        double *gscr = gd ? (double *)malloc(sizeof(double) * gd) : nullptr;
-        for (int i = 0; i < gd; i++) gscr[i] = NAN;
-        const int sdn = mmpc_soc_doubles(N, D::NX, D::NU, MC + D::NSELF);
-        double *soc = (double *)malloc(sizeof(double) * sdn);
-        for (int i = 0; i < sdn; i++) soc[i] = NAN;
+        double *lds = lds_b.next(L.total);
+        double *gscr = gscr_b.next(MmpcGainBlock<KIND, N>::total);
+        double *soc = soc_b.next(mmpc_soc_doubles(N, D::NX, D::NU, MC + D::NSELF));
         double *ob = obs_copy(obs, b, so);
         MmpcIO io;
-        mmpc_instance_io<KIND>(io, *P, b, N, so, x_init, traj_ref, u_ref, u_last, nullptr, obs, X, U, s, status, iters, cost, err, soc, 0);
+        mmpc_instance_io<KIND>(io, *P, b, N, so, x_init, traj_ref, u_ref, u_last, x_guess, obs, X, U, s, status, iters, cost, err, soc, 0);
         io.obs = ob;
         io.state = state ? state + (size_t)b * sd : nullptr; io.budget = budget; io.resume = resume; io.gscr = gscr;
         if (P->obs_per_stage == 2 && tick) io.tick = tick + b;
         MmpcEmu emu = reverse ? MmpcEmu{63, -1, -1} : MmpcEmu{0, 64, 1};
         if (budget > 0 || resume) mmpc_solve_fast<KIND, N, MC, true>(*P, io, lds, emu); else mmpc_solve_fast<KIND, N, MC, false>(*P, io, lds, emu);
-        free(ob); free(gscr); free(soc); free(lds);
+        free(ob);
     }
 }
 
@@ -86,15 +81,23 @@ extern "C" int mmpc_emum_solve(int kind, const MmpcParams *P, int B, const doubl
 #ifndef MMPC_EMUM_SHAPES   // (the sanitizer build instantiates one of them: it compiles for minutes per shape)
 #define MMPC_EMUM_SHAPES(X) X(0, 20, 5) X(0, 30, 8) X(0, 20, 3) X(1, 15, 3)
 #endif
-// specialised kernels; budget > 0 / resume as mmpc_fast_kernel (state: [B][mmpc_emum_fast_state_doubles]); -1: no such shape
+// specialised kernels; budget > 0 / resume as mmpc_fast_kernel (state: [B][mmpc_emum_fast_state_doubles]); x_guess: [B][N+1][NX], the
+// launch argument of the same name, or null; -1: no such shape
+extern "C" int mmpc_emum_solve_fast_guess(int kind, const MmpcParams *P, int B, const double *x_init, const double *traj_ref,
+                                          const double *u_ref, const double *u_last, const double *obs, const long long *tick, double *X,
+                                          double *U, double *s, int *status, int *iters, double *cost, double *err, int reverse, int budget,
+                                          double *state, int resume, const double *x_guess) {
+#define MMPC_X(K, NN, MM) if (kind == K && P->N == NN && P->M == MM) { run_fast<K, NN, MM>(P, B, x_init, traj_ref, u_ref, u_last, obs, tick, X, U, s, status, iters, cost, err, reverse, budget, state, resume, x_guess); return 0; }
+    MMPC_EMUM_SHAPES(MMPC_X)
+#undef MMPC_X
+    return -1;
+}
 extern "C" int mmpc_emum_solve_fast(int kind, const MmpcParams *P, int B, const double *x_init, const double *traj_ref,
                                     const double *u_ref, const double *u_last, const double *obs, const long long *tick, double *X,
                                     double *U, double *s, int *status, int *iters, double *cost, double *err, int reverse, int budget,
                                     double *state, int resume) {
-#define MMPC_X(K, NN, MM) if (kind == K && P->N == NN && P->M == MM) { run_fast<K, NN, MM>(P, B, x_init, traj_ref, u_ref, u_last, obs, tick, X, U, s, status, iters, cost, err, reverse, budget, state, resume); return 0; }
-    MMPC_EMUM_SHAPES(MMPC_X)
-#undef MMPC_X
-    return -1;
+    return mmpc_emum_solve_fast_guess(kind, P, B, x_init, traj_ref, u_ref, u_last, obs, tick, X, U, s, status, iters, cost, err, reverse, budget,
+                                      state, resume, nullptr);
 }
 extern "C" int mmpc_emum_fast_state_doubles(int kind, int N, int M) {
 #define MMPC_X(K, NN, MM) if (kind == K && N == NN && M == MM) return mmpc_fast_state_doubles<K, NN>(MM);

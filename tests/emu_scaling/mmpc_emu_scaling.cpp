@@ -5,6 +5,7 @@
 // wrappers set them, and an X guess.  With scale_max_grad = 0 the entry points are plain solves, so one library solves an
 // instance with the option on and its twin with scaled weights and the option off.
 #define MMPC_EMU 1
+#include "../emu_common/mmpc_emu_poison.h"
 #include "../../mobile-manipulator-mpc_amd/csrc/mmpc_fast.h"
 #include <stdlib.h>
 #include <string.h>
@@ -29,12 +30,10 @@ static void run(const MmpcParams *P, int B, const double *x_init, const double *
     const MmpcLayout L = mmpc_layout<KIND>(N, M, P->obs_per_stage, (KIND == 0 && P->L > 0) ? 6 : 0,
                                            (KIND == 0 && P->L >= 2 && P->as_written) ? 6 * (P->L - 1) : 0);
     const size_t so = obs_stride(P, N, M);
+    MmpcEmuBlock lds_b, soc_b;   // (mmpc_emu_poison.h: what the blocks hold at the start of an instance is the caller's choice, NaN by default)
     for (int b = 0; b < B; b++) {
-        double *lds = (double *)malloc(sizeof(double) * L.total);
-        for (int i = 0; i < L.total; i++) lds[i] = NAN;
-        const int sdn = mmpc_soc_doubles(N, D::NX, D::NU, L.NR);
-        double *soc = (double *)malloc(sizeof(double) * sdn);
-        for (int i = 0; i < sdn; i++) soc[i] = NAN;
+        double *lds = lds_b.next(L.total);
+        double *soc = soc_b.next(mmpc_soc_doubles(N, D::NX, D::NU, L.NR));
         double *ob = obs_copy(obs, b, so);
         MmpcIO io;
         mmpc_instance_io<KIND>(io, *P, b, N, so, x_init, traj_ref, u_ref, u_last, x_guess, obs, X, U, s, status, iters, cost, err, soc, 0);
@@ -42,7 +41,7 @@ static void run(const MmpcParams *P, int B, const double *x_init, const double *
         io.scale_max_grad = scale_max_grad; if (scale_out) io.scale_out = scale_out + b;
         MmpcEmu emu = reverse ? MmpcEmu{63, -1, -1} : MmpcEmu{0, 64, 1};
         mmpc_solve_one<KIND>(*P, io, lds, emu);
-        free(ob); free(soc); free(lds);
+        free(ob);
     }
 }
 
@@ -54,16 +53,12 @@ static void run_fast(const MmpcParams *P, int B, const double *x_init, const dou
     const MmpcFastLayout L = mmpc_fast_layout<KIND, N>(MC, P->obs_per_stage);
     const size_t so = obs_stride(P, N, MC);
     const int sd = mmpc_fast_state_doubles<KIND, N>(MC);
+    MmpcEmuBlock lds_b, gscr_b, soc_b;
     for (int b = 0; b < B; b++) {
         if (resume && status[b] != 3) continue;   // a continuation launch only runs the suspended instances
-        double *lds = (double *)malloc(sizeof(double) * L.total);
-        for (int i = 0; i < L.total; i++) lds[i] = NAN;
-        const int gd = MmpcGainBlock<KIND, N>::total;
-        double *gscr = gd ? (double *)malloc(sizeof(double) * gd) : nullptr;
-        for (int i = 0; i < gd; i++) gscr[i] = NAN;
-        const int sdn = mmpc_soc_doubles(N, D::NX, D::NU, MC + D::NSELF);
-        double *soc = (double *)malloc(sizeof(double) * sdn);
-        for (int i = 0; i < sdn; i++) soc[i] = NAN;
+        double *lds = lds_b.next(L.total);
+        double *gscr = gscr_b.next(MmpcGainBlock<KIND, N>::total);
+        double *soc = soc_b.next(mmpc_soc_doubles(N, D::NX, D::NU, MC + D::NSELF));
         double *ob = obs_copy(obs, b, so);
         MmpcIO io;
         mmpc_instance_io<KIND>(io, *P, b, N, so, x_init, traj_ref, u_ref, u_last, x_guess, obs, X, U, s, status, iters, cost, err, soc, 0);
@@ -72,7 +67,7 @@ static void run_fast(const MmpcParams *P, int B, const double *x_init, const dou
         io.scale_max_grad = scale_max_grad; if (scale_out) io.scale_out = scale_out + b;
         MmpcEmu emu = reverse ? MmpcEmu{63, -1, -1} : MmpcEmu{0, 64, 1};
         if (budget > 0 || resume) mmpc_solve_fast<KIND, N, MC, true>(*P, io, lds, emu); else mmpc_solve_fast<KIND, N, MC, false>(*P, io, lds, emu);
-        free(ob); free(gscr); free(soc); free(lds);
+        free(ob);
     }
 }
 

@@ -6,6 +6,7 @@
 // operation by operation).  -DMMPC_EMUSH_MAIN adds a main(): the stand-alone program of the sanitizer run, which solves the
 // instances of a file written by shape_helper.write_case and exits 0 when every one of them converged.
 #define MMPC_EMU 1
+#include "../emu_common/mmpc_emu_poison.h"
 #include "../../mobile-manipulator-mpc_amd/csrc/mmpc_fast.h"
 #include <stdio.h>
 #include <stdlib.h>
@@ -34,12 +35,10 @@ static void run(const MmpcParams *P, int B, const double *x_init, const double *
     const int N = P->N, M = P->M;
     const MmpcLayout L = mmpc_layout<KIND>(N, M, P->obs_per_stage, 0, 0);
     const size_t so = obs_stride(P, N, M);
+    MmpcEmuBlock lds_b, soc_b;   // (mmpc_emu_poison.h: what the blocks hold at the start of an instance is the caller's choice, NaN by default)
     for (int b = 0; b < B; b++) {
-        double *lds = (double *)malloc(sizeof(double) * L.total);
-        for (int i = 0; i < L.total; i++) lds[i] = NAN;
-        const int sdn = mmpc_soc_doubles(N, D::NX, D::NU, L.NR);
-        double *soc = (double *)malloc(sizeof(double) * sdn);
-        for (int i = 0; i < sdn; i++) soc[i] = NAN;
+        double *lds = lds_b.next(L.total);
+        double *soc = soc_b.next(mmpc_soc_doubles(N, D::NX, D::NU, L.NR));
         double *ob = obs_copy(obs, b, so);
         MmpcIO io;
         mmpc_instance_io<KIND>(io, *P, b, N, so, x_init, traj_ref, u_ref, u_last, nullptr, obs, X, U, s, status, iters, cost, err, soc, 0);
@@ -47,37 +46,33 @@ static void run(const MmpcParams *P, int B, const double *x_init, const double *
         if (P->obs_per_stage == 2 && tick) io.tick = tick + b;
         MmpcEmu emu = reverse ? MmpcEmu{63, -1, -1} : MmpcEmu{0, 64, 1};
         mmpc_solve_one<KIND>(*P, io, lds, emu);
-        free(ob); free(soc); free(lds);
+        free(ob);
     }
 }
 
 template <int KIND, int N, int MC>
 static void run_fast(const MmpcParams *P, int B, const double *x_init, const double *traj_ref, const double *u_ref, const double *u_last,
                      const double *obs, const long long *tick, double *X, double *U, double *s, int *status, int *iters, double *cost,
-                     double *err, int reverse, int budget, double *state, int resume) {
+                     double *err, int reverse, int budget, double *state, int resume, const double *x_guess = nullptr) {
     typedef MmpcDims<KIND> D;
     const MmpcFastLayout L = mmpc_fast_layout<KIND, N>(MC, P->obs_per_stage);
     const size_t so = obs_stride(P, N, MC);
     const int sd = mmpc_fast_state_doubles<KIND, N>(MC);
+    MmpcEmuBlock lds_b, gscr_b, soc_b;
     for (int b = 0; b < B; b++) {
         if (resume && status[b] != 3) continue;   // a continuation launch only runs the suspended instances
-        double *lds = (double *)malloc(sizeof(double) * L.total);
-        for (int i = 0; i < L.total; i++) lds[i] = NAN;
-        const int gd = MmpcGainBlock<KIND, N>::total;
-        double *gscr = gd ? (double *)malloc(sizeof(double) * gd) : nullptr;
-        for (int i = 0; i < gd; i++) gscr[i] = NAN;
-        const int sdn = mmpc_soc_doubles(N, D::NX, D::NU, MC + D::NSELF);
-        double *soc = (double *)malloc(sizeof(double) * sdn);
-        for (int i = 0; i < sdn; i++) soc[i] = NAN;
+        double *lds = lds_b.next(L.total);
+        double *gscr = gscr_b.next(MmpcGainBlock<KIND, N>::total);
+        double *soc = soc_b.next(mmpc_soc_doubles(N, D::NX, D::NU, MC + D::NSELF));
         double *ob = obs_copy(obs, b, so);
         MmpcIO io;
-        mmpc_instance_io<KIND>(io, *P, b, N, so, x_init, traj_ref, u_ref, u_last, nullptr, obs, X, U, s, status, iters, cost, err, soc, 0);
+        mmpc_instance_io<KIND>(io, *P, b, N, so, x_init, traj_ref, u_ref, u_last, x_guess, obs, X, U, s, status, iters, cost, err, soc, 0);
         io.obs = ob;
         io.state = state ? state + (size_t)b * sd : nullptr; io.budget = budget; io.resume = resume; io.gscr = gscr;
         if (P->obs_per_stage == 2 && tick) io.tick = tick + b;
         MmpcEmu emu = reverse ? MmpcEmu{63, -1, -1} : MmpcEmu{0, 64, 1};
         if (budget > 0 || resume) mmpc_solve_fast<KIND, N, MC, true>(*P, io, lds, emu); else mmpc_solve_fast<KIND, N, MC, false>(*P, io, lds, emu);
-        free(ob); free(gscr); free(soc); free(lds);
+        free(ob);
     }
 }
 
@@ -91,15 +86,23 @@ extern "C" int mmpc_emush_solve(int kind, const MmpcParams *P, int B, const doub
     run<MMPC_EMUSH_KIND>(P, B, x_init, traj_ref, u_ref, u_last, obs, tick, X, U, s, status, iters, cost, err, reverse);
     return 0;
 }
-// the specialised kernel; budget > 0 / resume as mmpc_fast_kernel (state: [B][mmpc_emush_fast_state_doubles]); -1: not this library's shape
+// the specialised kernel; budget > 0 / resume as mmpc_fast_kernel (state: [B][mmpc_emush_fast_state_doubles]); x_guess: [B][N+1][NX], the
+// launch argument of the same name, or null; -1: not this library's shape
+extern "C" int mmpc_emush_solve_fast_guess(int kind, const MmpcParams *P, int B, const double *x_init, const double *traj_ref,
+                                           const double *u_ref, const double *u_last, const double *obs, const long long *tick, double *X,
+                                           double *U, double *s, int *status, int *iters, double *cost, double *err, int reverse, int budget,
+                                           double *state, int resume, const double *x_guess) {
+    if (!shape_of(kind, P)) return -1;
+    run_fast<MMPC_EMUSH_KIND, MMPC_EMUSH_N, MMPC_EMUSH_M>(P, B, x_init, traj_ref, u_ref, u_last, obs, tick, X, U, s, status, iters, cost, err,
+                                                          reverse, budget, state, resume, x_guess);
+    return 0;
+}
 extern "C" int mmpc_emush_solve_fast(int kind, const MmpcParams *P, int B, const double *x_init, const double *traj_ref,
                                      const double *u_ref, const double *u_last, const double *obs, const long long *tick, double *X,
                                      double *U, double *s, int *status, int *iters, double *cost, double *err, int reverse, int budget,
                                      double *state, int resume) {
-    if (!shape_of(kind, P)) return -1;
-    run_fast<MMPC_EMUSH_KIND, MMPC_EMUSH_N, MMPC_EMUSH_M>(P, B, x_init, traj_ref, u_ref, u_last, obs, tick, X, U, s, status, iters, cost, err,
-                                                          reverse, budget, state, resume);
-    return 0;
+    return mmpc_emush_solve_fast_guess(kind, P, B, x_init, traj_ref, u_ref, u_last, obs, tick, X, U, s, status, iters, cost, err, reverse, budget,
+                                       state, resume, nullptr);
 }
 extern "C" int mmpc_emush_fast_state_doubles() { return mmpc_fast_state_doubles<MMPC_EMUSH_KIND, MMPC_EMUSH_N>(MMPC_EMUSH_M); }
 extern "C" int mmpc_emush_fast_state_scal_offset() { return mmpc_fast_state_scal_offset<MMPC_EMUSH_KIND, MMPC_EMUSH_N>(); }   // (the scalars of the save area)

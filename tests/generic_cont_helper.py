@@ -33,7 +33,7 @@ HS2 = np.array([[0.6, 0.0, 0.35 + 0.606 + 0.333, _R2, 0, _R2], [0.6, 0.0, 0.35 +
 
 def build():
     out = os.path.join(_HERE, "emu_generic_cont", "_build", "libmmpc_emu_gcont.so")
-    deps = [_SRC] + [os.path.join(_CSRC, f) for f in os.listdir(_CSRC) if f.endswith((".h", ".inc"))]
+    deps = [_SRC, emu_helper.POISON_H] + [os.path.join(_CSRC, f) for f in os.listdir(_CSRC) if f.endswith((".h", ".inc"))]
     if not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(f) for f in deps):
         os.makedirs(os.path.dirname(out), exist_ok=True)
         tmp = out + ".tmp.%d" % os.getpid()

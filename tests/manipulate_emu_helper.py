@@ -11,7 +11,7 @@ import tick_emu_helper as TH
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _SRC = os.path.join(_HERE, "manipulate_emu", "mmpc_manipulate_emu.cpp")
 _CSRC = os.path.join(_HERE, "..", "mobile-manipulator-mpc_amd", "csrc")
-_DEPS = [_SRC, os.path.join(_HERE, "..", "include", "mmpc.h")] + [os.path.join(_CSRC, f) for f in ("mmpc_manipulate.h", "mmpc_ik.h", "mmpc_tick.h", "mmpc_core.h", "mmpc_tile.h")]
+_DEPS = [_SRC, os.path.join(_HERE, "emu_common", "mmpc_emu_poison.h"), os.path.join(_HERE, "..", "include", "mmpc.h")] + [os.path.join(_CSRC, f) for f in ("mmpc_manipulate.h", "mmpc_ik.h", "mmpc_tick.h", "mmpc_core.h", "mmpc_tile.h")]
 
 DONE, MANIPULATE, MANIP_DONE = 3, 4, 5
 BX, BZ = -0.007, 0.606 + 0.333

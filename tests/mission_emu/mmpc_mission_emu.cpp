@@ -4,6 +4,7 @@
 // robots in the opposite order too (the lists may come in any order).  The arguments are those of mmpc_mission_prepare_device, with
 // the handle replaced by what the kernel reads of it; the counts are zeroed here, as the entry point does before its launch.
 #define MMPC_EMU 1
+#include "../emu_common/mmpc_emu_poison.h"
 #include "../../mobile-manipulator-mpc_amd/csrc/mmpc_mission.h"
 #include <stdlib.h>
 
@@ -16,14 +17,13 @@ extern "C" int mmpc_mission_emu_prepare(int N, int M, double dt, const double *x
     P->N = N; P->M = M; P->obs_per_stage = 1; P->dt = dt;
     for (int r = 0; r < 2; r++) for (int j = 0; j < 9; j++) P->xlim[r][j] = xlim[r * 9 + j];
     for (int i = 0; i < 4; i++) counts[i] = 0;
+    MmpcEmuBlock lds_b;   // (mmpc_emu_poison.h: what the slab holds at the start of a robot is the caller's choice, NaN by default)
     for (int i = 0; i < B; i++) {
         const int b = reverse ? B - 1 - i : i;
         // exact-size heap slab so that a sanitizer build sees any access outside it
-        double *lds = (double *)malloc(sizeof(double) * MMPC_TICK_LDS);
-        for (int j = 0; j < MMPC_TICK_LDS; j++) lds[j] = NAN;
+        double *lds = lds_b.next(MMPC_TICK_LDS);
         MmpcEmu emu = reverse ? MmpcEmu{63, -1, -1} : MmpcEmu{0, 64, 1};
         mmpc_mission_robot(*P, b, B, x, tick, phase, U_prev, glob, nglob, obs0, vel, x_in, traj_ref, start, obs, lists, counts, lds, emu);
-        free(lds);
     }
     free(P);
     return 0;

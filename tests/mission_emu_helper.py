@@ -11,7 +11,7 @@ import tick_emu_helper as TH
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _SRC = os.path.join(_HERE, "mission_emu", "mmpc_mission_emu.cpp")
 _CSRC = os.path.join(_HERE, "..", "mobile-manipulator-mpc_amd", "csrc")
-_DEPS = [_SRC, os.path.join(_HERE, "..", "include", "mmpc.h")] + [os.path.join(_CSRC, f) for f in ("mmpc_mission.h", "mmpc_tick.h", "mmpc_core.h", "mmpc_tile.h")]
+_DEPS = [_SRC, os.path.join(_HERE, "emu_common", "mmpc_emu_poison.h"), os.path.join(_HERE, "..", "include", "mmpc.h")] + [os.path.join(_CSRC, f) for f in ("mmpc_mission.h", "mmpc_tick.h", "mmpc_core.h", "mmpc_tile.h")]
 
 MOVE, APPROACH, ROTATE, DONE = 0, 1, 2, 3
 ANGLE_TOL = 0.5 * 3.141592653589793 / 180

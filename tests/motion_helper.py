@@ -22,7 +22,7 @@ TICKS = np.array([0, 1, 7, 2 ** 31 + 5, 3, 250, 2 ** 31 + 77, 12], np.int64)
 
 def build(asan=False):
     out = os.path.join(_HERE, "emu_motion", "_build", "libmmpc_emu_motion_asan.so" if asan else "libmmpc_emu_motion.so")
-    deps = [_SRC] + [os.path.join(_CSRC, f) for f in os.listdir(_CSRC) if f.endswith((".h", ".inc"))]
+    deps = [_SRC, emu_helper.POISON_H] + [os.path.join(_CSRC, f) for f in os.listdir(_CSRC) if f.endswith((".h", ".inc"))]
     if not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(f) for f in deps):
         os.makedirs(os.path.dirname(out), exist_ok=True)
         flags = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-omit-frame-pointer", "-DMMPC_EMUM_SHAPES(X)=X(0, 30, 8)"] if asan else ["-O2"]

@@ -25,7 +25,7 @@ GENERIC = [("wb", 6, 2), ("base", 5, 1), ("pose", 6, 2), ("wb-guess", 6, 2)]
 
 def build():
     out = os.path.join(_HERE, "emu_scaling", "_build", "libmmpc_emu_scaling.so")
-    deps = [_SRC] + [os.path.join(_CSRC, f) for f in os.listdir(_CSRC) if f.endswith((".h", ".inc"))]
+    deps = [_SRC, emu_helper.POISON_H] + [os.path.join(_CSRC, f) for f in os.listdir(_CSRC) if f.endswith((".h", ".inc"))]
     if not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(f) for f in deps):
         os.makedirs(os.path.dirname(out), exist_ok=True)
         subprocess.check_call(["g++", "-std=c++17", "-fPIC", "-shared", "-Wno-unknown-pragmas", "-O2", "-o", out, _SRC])

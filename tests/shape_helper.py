@@ -44,7 +44,7 @@ def build(shape, asan_main=False):
     """the host library of one shape; asan_main: the stand-alone sanitized program (its own main) instead"""
     k, n, m = shape
     out = os.path.join(_BUILD, ("mmpc_emu_shape_asan_%d_%d_%d" if asan_main else "libmmpc_emu_shape_%d_%d_%d.so") % (k, n, m))
-    deps = [_SRC] + [os.path.join(_CSRC, f) for f in os.listdir(_CSRC) if f.endswith((".h", ".inc"))]
+    deps = [_SRC, emu_helper.POISON_H] + [os.path.join(_CSRC, f) for f in os.listdir(_CSRC) if f.endswith((".h", ".inc"))]
     if not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(f) for f in deps):
         os.makedirs(_BUILD, exist_ok=True)
         # (the sanitizers' runtimes linked into the program: it then runs under whatever the environment preloads, untouched)

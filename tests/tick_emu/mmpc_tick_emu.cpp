@@ -3,6 +3,7 @@
 // lanes; `reverse` runs the lanes of every phase in the opposite order (a result that changes exposes an intra-phase race).
 // The arguments are those of mmpc_tick_prepare_device, with the handle replaced by what the kernel reads of it.
 #define MMPC_EMU 1
+#include "../emu_common/mmpc_emu_poison.h"
 #include "../../mobile-manipulator-mpc_amd/csrc/mmpc_tick.h"
 #include <stdlib.h>
 
@@ -14,13 +15,12 @@ extern "C" int mmpc_tick_emu_prepare(int N, int M, double dt, const double *xlim
     MmpcParams *P = (MmpcParams *)calloc(1, sizeof(MmpcParams));
     P->N = N; P->M = M; P->obs_per_stage = 1; P->dt = dt;
     for (int r = 0; r < 2; r++) for (int j = 0; j < 9; j++) P->xlim[r][j] = xlim[r * 9 + j];
+    MmpcEmuBlock lds_b;   // (mmpc_emu_poison.h: what the slab holds at the start of a robot is the caller's choice, NaN by default)
     for (int b = 0; b < B; b++) {
         // exact-size heap slab so that a sanitizer build sees any access outside it
-        double *lds = (double *)malloc(sizeof(double) * MMPC_TICK_LDS);
-        for (int i = 0; i < MMPC_TICK_LDS; i++) lds[i] = NAN;
+        double *lds = lds_b.next(MMPC_TICK_LDS);
         MmpcEmu emu = reverse ? MmpcEmu{63, -1, -1} : MmpcEmu{0, 64, 1};
         mmpc_tick_robot(*P, b, x, tick, U_prev, glob, nglob, obs0, vel, x_in, traj_ref, start, obs, u_guess, x_guess, lds, emu);
-        free(lds);
     }
     free(P);
     return 0;

@@ -9,7 +9,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _SRC = os.path.join(_HERE, "tick_emu", "mmpc_tick_emu.cpp")
 _CSRC = os.path.join(_HERE, "..", "mobile-manipulator-mpc_amd", "csrc")
-_DEPS = [_SRC] + [os.path.join(_CSRC, f) for f in ("mmpc_tick.h", "mmpc_core.h", "mmpc_tile.h")]
+_DEPS = [_SRC, os.path.join(_HERE, "emu_common", "mmpc_emu_poison.h")] + [os.path.join(_CSRC, f) for f in ("mmpc_tick.h", "mmpc_core.h", "mmpc_tile.h")]
 
 
 def build():
