@@ -379,6 +379,73 @@ int mmpc_manipulate_prepare_device(mmpc_handle h, int B, double *d_x, long long 
 int mmpc_shift_guess_device(mmpc_handle h, int B, const int *d_phase, const double *d_U_prev, const double *d_x_in,
                             double *d_u_guess, double *d_x_guess, void *stream);
 
+/* ---- Missions under iteration budgets: the glue per robot (csrc/mmpc_round.h).  Under a budget a robot whose solve was suspended is
+ * continued on a side stream while the others go on, so only some robots take part in a round.  d_hold [B] (int32) says which: */
+#define MMPC_HOLD_NEW 0       /* not solved yet: the next round does not advance the robot */
+#define MMPC_HOLD_READY 1     /* d_U_last[b] is its latest optimum: the next round advances it with U_last[b][0] */
+#define MMPC_HOLD_LISTED 2    /* in a solve list of the current round (between a round call and the commit) */
+#define MMPC_HOLD_RETIRED 3   /* has taken tick_limit ticks and its last plant step: never touched again */
+#define MMPC_HOLD_RETIRED_AT_DONE 4 /* retired by the mission round at MMPC_PHASE_DONE: the manipulate round, where one runs, makes
+                                     * the output-less transition of the lock step's last call and sets RETIRED; else it stays */
+#define MMPC_HOLD_SUSPENDED 8 /* + s: its continuation is in flight on handle set s (s >= 0) */
+
+/* mmpc_mission_prepare_device per robot.  The arguments, handle requirements, argument checks, B = 0, stream ordering, the
+ * hipMemsetAsync of the four counts and "no allocation, copy or synchronisation" are that call's; d_U_last [B][N][5] (required)
+ * takes the place of d_U_prev, and d_tick, d_hold [B], d_solve_phase [B] (int32) are required as well; tick_limit >= 1 (else
+ * MMPC_E_ARG).  Per robot b:
+ *   - d_hold[b] neither NEW nor READY: skipped.  Nothing of the robot is read for output or written; it enters no list and no count;
+ *   - a robot frozen on entry (phase code outside 0..2) increments d_counts[3] and nothing else, as in the prepare call;
+ *   - READY and d_tick[b] + 1 >= tick_limit: the robot retires.  It gets what the prepare call without outputs does to it (plant step
+ *     with d_U_last[b][0], state machine; d_x, d_tick, d_phase written), writes no output, enters no list and no count, and
+ *     d_hold[b] = RETIRED - or RETIRED_AT_DONE when the step took it to MMPC_PHASE_DONE;
+ *   - otherwise exactly the steps of mmpc_mission_prepare_device, with the advance decided per robot: READY advances with
+ *     d_U_last[b][0], NEW does not.  A robot that enters list p gets d_hold[b] = LISTED and d_solve_phase[b] = p; one that reaches
+ *     MMPC_PHASE_DONE keeps its hold.
+ * A round of a mission under budgets is: mmpc_mission_commit_device(rejoin = 1) for the handle set whose continuations have come
+ * back; this call; mmpc_manipulate_round_device when the phase is on; mmpc_shift_guess_device with d_solve_phase as d_phase and
+ * d_U_last as d_U_prev (shifted warm start); mmpc_solve_rows_device on the budgeted handles of the set with d_u_last = d_U_last;
+ * mmpc_mission_commit_device(rejoin = 0); mmpc_resume_batch_device per handle on side streams (fleet.py:DeviceFleet.run_mission). */
+int mmpc_mission_round_device(mmpc_handle h, int B, double *d_x, long long *d_tick, int *d_phase, const double *d_U_last,
+                              const double *d_glob, int nglob, const double *d_obs0, const double *d_vel, double *d_x_in,
+                              double *d_traj_ref, int *d_start, double *d_obs, int *d_lists, int *d_counts, int *d_hold,
+                              int *d_solve_phase, long long tick_limit, void *stream);
+
+/* mmpc_manipulate_prepare_device per robot, after mmpc_mission_round_device on the same arrays; everything not named here is that
+ * call's, d_U_last, d_tick, d_hold, d_solve_phase and tick_limit as in mmpc_mission_round_device.  Per robot b:
+ *   - d_hold[b] == RETIRED_AT_DONE: the transition of the prepare call without outputs (IK, d_qgoal, d_ik_status, d_plan, finish test,
+ *     d_phase = 4 or 5), no output, no list, no count; d_hold[b] = RETIRED;
+ *   - d_hold[b] neither NEW nor READY otherwise: skipped as above;
+ *   - READY, phase 4 and d_tick[b] + 1 >= tick_limit: retires - the prepare call without outputs (plant step, finish test), no list,
+ *     no count, d_hold[b] = RETIRED;
+ *   - otherwise exactly the steps of mmpc_manipulate_prepare_device: a READY robot in phase 4 advances with d_U_last[b][0], one at
+ *     phase 3 (advanced by the mission round) makes the transition.  A robot that enters the list gets d_hold[b] = LISTED and
+ *     d_solve_phase[b] = 4. */
+int mmpc_manipulate_round_device(mmpc_handle h, int B, double *d_x, long long *d_tick, int *d_phase, const double *d_U_last,
+                                 const double *d_pose, int nplan, double *d_plan, double *d_qgoal, int *d_ik_status,
+                                 const double *d_obs0, const double *d_vel, double *d_x_in, double *d_traj_ref, int *d_start,
+                                 double *d_obs, int *d_list, int *d_counts, int *d_hold, int *d_solve_phase, long long tick_limit,
+                                 void *stream);
+
+/* Takes the solves of a round into the fleet's state: one launch, one 64-lane workgroup per robot.  Whole-body handles only (N comes
+ * from the handle).  All arrays are required: d_hold, d_solve_phase [B]; of the output set d_U [B][N][5], d_status, d_iters [B];
+ * d_tick [B] (int64), d_phase [B]; d_U_last [B][N][5] (not d_U); the histories d_u0 [B][T][5], d_iters_hist, d_status_hist,
+ * d_phase_hist [B][T] (int32), T >= 1; d_counters [4] (int32) = committed, suspended, failed, live, zeroed by one hipMemsetAsync
+ * queued before the kernel.  set must be in 0..15, rejoin 0 or 1.  A robot is handled when d_hold[b] == LISTED and rejoin == 0, or
+ * d_hold[b] == SUSPENDED + set and rejoin == 1; no other robot is written:
+ *   - d_status[b] == 3 (suspended: the budget is used up) and rejoin == 0: d_hold[b] = SUSPENDED + set, d_solve_phase[b] = -1,
+ *     counters[1] += 1;
+ *   - any other status: d_U_last[b] = d_U[b]; with t = d_tick[b] in 0..T-1, row [b][t] of the histories = d_U[b][0], d_iters[b],
+ *     d_status[b], d_phase[b]; d_hold[b] = READY, d_solve_phase[b] = -1; counters[0] += 1, and counters[2] += 1 when the status is
+ *     not 0 (a failed solve does not stop a robot).
+ * counters[3] counts, over ALL robots after the above, those the run still has work for: hold NEW, LISTED, SUSPENDED + any set, or
+ * READY with a phase in {0, 1, 2, 4}.  Missing array, d_U_last == d_U, bad set / rejoin / T or B > max_batch: MMPC_E_ARG.  B = 0 is
+ * a no-op.  Asynchronous on `stream`, ordered against the handle's other launches as mmpc_mission_prepare_device is; no allocation,
+ * copy or synchronisation inside. */
+int mmpc_mission_commit_device(mmpc_handle h, int B, int *d_hold, int *d_solve_phase, int set, int rejoin, const double *d_U,
+                               const int *d_status, const int *d_iters, const long long *d_tick, const int *d_phase, double *d_U_last,
+                               double *d_u0, int *d_iters_hist, int *d_status_hist, int *d_phase_hist, int T, int *d_counters,
+                               void *stream);
+
 /* Streams and threads: a handle owns device state that its launches read and write (parameter block, schedule hint,
  * warm start).  Calls on one handle must come from one host thread at a time.  Launches may use different streams:
  * a launch on another stream than the handle's previous one is ordered after it (event wait), and the entry points

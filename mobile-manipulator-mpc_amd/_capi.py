@@ -12,6 +12,7 @@ KIND_WHOLEBODY, KIND_BASE, KIND_WHOLEBODY_POSE = 0, 1, 2
 STATUS_CONVERGED, STATUS_MAXITER, STATUS_NUMERIC, STATUS_SUSPENDED = 0, 1, 2, 3
 PHASE_MOVE, PHASE_APPROACH, PHASE_ROTATE, PHASE_DONE = 0, 1, 2, 3      # MMPC_PHASE_*: mission_prepare
 PHASE_MANIPULATE, PHASE_MANIP_DONE = 4, 5                              # ... and manipulate_prepare
+HOLD_NEW, HOLD_READY, HOLD_LISTED, HOLD_RETIRED, HOLD_RETIRED_AT_DONE, HOLD_SUSPENDED = 0, 1, 2, 3, 4, 8   # MMPC_HOLD_*: mission_round
 STATUS_Q8_REFUSED = 8      # host-side only (controllers/_q8.py): converged, but an as-written extra half-space row is violated
 
 
@@ -29,6 +30,7 @@ EXPORTS = ["mmpc_create", "mmpc_destroy", "mmpc_set_weights", "mmpc_set_terminal
            "mmpc_lds_bytes", "mmpc_problems_per_cu", "mmpc_set_warm_start", "mmpc_set_schedule_hint", "mmpc_set_iteration_budget", "mmpc_resume_batch_device", "mmpc_solve_list_device", "mmpc_suspended_count", "mmpc_last_error", "mmpc_version", "mmpc_ik_batch", "mmpc_ik_batch_device",
            "mmpc_tick_prepare_device", "mmpc_set_obstacle_clock", "mmpc_set_objective_scaling",
            "mmpc_mission_prepare_device", "mmpc_manipulate_prepare_device", "mmpc_solve_rows_device", "mmpc_shift_guess_device",
+           "mmpc_mission_round_device", "mmpc_manipulate_round_device", "mmpc_mission_commit_device",
            "mmpc_shape_supported", "mmpc_load_shape_library", "mmpc_runs_specialised", "mmpc_set_persistent_grid"]
 LISTED_SHAPES = ((KIND_WHOLEBODY, 20, 5), (KIND_WHOLEBODY, 30, 8), (KIND_WHOLEBODY, 20, 3), (KIND_BASE, 15, 3))   # MMPC_FAST_LIST
 
@@ -80,6 +82,9 @@ def lib():
         L.mmpc_mission_prepare_device.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 5 + [C.c_int] + [C.c_void_p] * 8 + [C.c_void_p]
         L.mmpc_manipulate_prepare_device.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 5 + [C.c_int] + [C.c_void_p] * 11 + [C.c_void_p]
         L.mmpc_shift_guess_device.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 5 + [C.c_void_p]
+        L.mmpc_mission_round_device.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 5 + [C.c_int] + [C.c_void_p] * 10 + [C.c_longlong, C.c_void_p]
+        L.mmpc_manipulate_round_device.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 5 + [C.c_int] + [C.c_void_p] * 13 + [C.c_longlong, C.c_void_p]
+        L.mmpc_mission_commit_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 10 + [C.c_int, C.c_void_p, C.c_void_p]
         L.mmpc_solve_rows_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 13 + [C.c_void_p]
         L.mmpc_set_obstacle_clock.argtypes = [C.c_void_p, C.c_void_p]
         L.mmpc_set_objective_scaling.argtypes = [C.c_void_p, C.c_double, C.c_void_p]
@@ -543,3 +548,90 @@ class Engine:
         p = lambda t_: C.c_void_p(t_.data_ptr()) if t_ is not None else None
         self._chk(lib().mmpc_shift_guess_device(self._h, B, p(phase), p(U_prev), p(x_in), p(u_guess), p(x_guess), C.c_void_p(st)),
                   "mmpc_shift_guess_device")
+
+    def _round_check(self, specs, required, dev):
+        for name, t_, shp, dt_ in specs:
+            if t_ is None:
+                if name in required:
+                    raise ValueError("%s is required" % name)
+                continue
+            if tuple(t_.shape) != shp or t_.dtype != dt_ or not t_.is_cuda or not t_.is_contiguous() or t_.device != dev:
+                raise ValueError("%s must be a contiguous %s tensor of shape %s on %s" % (name, dt_, shp, dev))
+
+    def mission_round(self, x, tick, phase, lists, counts, U_last, hold, solve_phase, tick_limit, glob=None, obs0=None, vel=None, x_in=None,
+                      traj_ref=None, start=None, obs=None, stream=None):
+        """mmpc_mission_round_device: mission_prepare per robot under the hold word (HOLD_*), asynchronous on torch's current stream (or
+        `stream`).  hold (B,) and solve_phase (B,) int32 are updated in place: a robot whose hold is HOLD_NEW (no advance) or HOLD_READY
+        (advance with U_last[b, 0]) gets the steps of mission_prepare and, when it enters list p, HOLD_LISTED and solve_phase = p; a
+        HOLD_READY robot with tick + 1 >= tick_limit retires (plant step and state machine, no output, no list); every other robot is
+        skipped.  U_last (B,N,5) is required; the other tensors as in mission_prepare."""
+        import torch
+        N, M = self.N, self.M
+        B = x.shape[0]
+        dev = x.device
+        ng = glob.shape[1] if glob is not None and glob.dim() == 3 else 0
+        f64, i64, i32 = torch.float64, torch.int64, torch.int32
+        self._round_check((("x", x, (B, 9), f64), ("tick", tick, (B,), i64), ("phase", phase, (B,), i32), ("lists", lists, (3, B), i32),
+                           ("counts", counts, (4,), i32), ("U_last", U_last, (B, N, 5), f64), ("hold", hold, (B,), i32),
+                           ("solve_phase", solve_phase, (B,), i32), ("glob", glob, (B, ng, 9), f64), ("obs0", obs0, (B, M, 3), f64),
+                           ("vel", vel, (B, M, 2), f64), ("x_in", x_in, (B, 9), f64), ("traj_ref", traj_ref, (B, N + 1, 9), f64),
+                           ("start", start, (B,), i32), ("obs", obs, (B, N + 1, M, 3), f64)),
+                          ("x", "tick", "phase", "lists", "counts", "U_last", "hold", "solve_phase", "glob"), dev)
+        st = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
+        p = lambda t_: C.c_void_p(t_.data_ptr()) if t_ is not None else None
+        self._chk(lib().mmpc_mission_round_device(self._h, B, p(x), p(tick), p(phase), p(U_last), p(glob), int(ng), p(obs0), p(vel), p(x_in),
+                                                  p(traj_ref), p(start), p(obs), p(lists), p(counts), p(hold), p(solve_phase), int(tick_limit),
+                                                  C.c_void_p(st)), "mmpc_mission_round_device")
+
+    def manipulate_round(self, x, tick, phase, pose, plan, lst, counts, U_last, hold, solve_phase, tick_limit, qgoal=None, ik_status=None,
+                         obs0=None, vel=None, x_in=None, traj_ref=None, start=None, obs=None, stream=None):
+        """mmpc_manipulate_round_device: manipulate_prepare per robot under the hold word, after mission_round on the same tensors;
+        asynchronous on torch's current stream (or `stream`).  A HOLD_NEW / HOLD_READY robot gets the steps of manipulate_prepare (a
+        HOLD_READY one in PHASE_MANIPULATE advances with U_last[b, 0]) and, when it enters the list, HOLD_LISTED and solve_phase = 4; a
+        HOLD_READY robot in PHASE_MANIPULATE with tick + 1 >= tick_limit retires; one the mission round retired at PHASE_DONE
+        (HOLD_RETIRED_AT_DONE) makes its transition without outputs and becomes HOLD_RETIRED; every other robot is skipped."""
+        import torch
+        N, M = self.N, self.M
+        B = x.shape[0]
+        dev = x.device
+        npl = plan.shape[1] if plan is not None and plan.dim() == 3 else 0
+        f64, i64, i32 = torch.float64, torch.int64, torch.int32
+        self._round_check((("x", x, (B, 9), f64), ("tick", tick, (B,), i64), ("phase", phase, (B,), i32), ("pose", pose, (B, 4), f64),
+                           ("plan", plan, (B, npl, 9), f64), ("lst", lst, (B,), i32), ("counts", counts, (2,), i32),
+                           ("U_last", U_last, (B, N, 5), f64), ("hold", hold, (B,), i32), ("solve_phase", solve_phase, (B,), i32),
+                           ("qgoal", qgoal, (B, 3), f64), ("ik_status", ik_status, (B,), i32), ("obs0", obs0, (B, M, 3), f64),
+                           ("vel", vel, (B, M, 2), f64), ("x_in", x_in, (B, 9), f64), ("traj_ref", traj_ref, (B, N + 1, 9), f64),
+                           ("start", start, (B,), i32), ("obs", obs, (B, N + 1, M, 3), f64)),
+                          ("x", "tick", "phase", "pose", "plan", "lst", "counts", "U_last", "hold", "solve_phase"), dev)
+        st = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
+        p = lambda t_: C.c_void_p(t_.data_ptr()) if t_ is not None else None
+        self._chk(lib().mmpc_manipulate_round_device(self._h, B, p(x), p(tick), p(phase), p(U_last), p(pose), int(npl), p(plan), p(qgoal),
+                                                     p(ik_status), p(obs0), p(vel), p(x_in), p(traj_ref), p(start), p(obs), p(lst), p(counts),
+                                                     p(hold), p(solve_phase), int(tick_limit), C.c_void_p(st)), "mmpc_manipulate_round_device")
+
+    def mission_commit(self, hold, solve_phase, set, rejoin, out, tick, phase, U_last, u0, iters_hist, status_hist, phase_hist, counters,
+                       stream=None):
+        """mmpc_mission_commit_device: takes a round's solves (out["U"], out["status"], out["iters"]) into U_last (B,N,5) and row
+        [b, tick[b]] of the histories u0 (B,T,5), iters_hist, status_hist, phase_hist (B,T) int32, for the robots with HOLD_LISTED
+        (rejoin = 0) or HOLD_SUSPENDED + set (rejoin = 1), which become HOLD_READY - or, with status 3 and rejoin = 0, HOLD_SUSPENDED +
+        set.  counters (4,) int32 = committed, suspended, failed, live (over all robots).  Asynchronous on torch's current stream (or
+        `stream`)."""
+        import torch
+        N = self.N
+        B = hold.shape[0]
+        dev = hold.device
+        T = u0.shape[1] if u0 is not None and u0.dim() == 3 else 0
+        f64, i64, i32 = torch.float64, torch.int64, torch.int32
+        names = ("hold", "solve_phase", "U", "status", "iters", "tick", "phase", "U_last", "u0", "iters_hist", "status_hist", "phase_hist", "counters")
+        self._round_check((("hold", hold, (B,), i32), ("solve_phase", solve_phase, (B,), i32), ("U", out["U"], (B, N, 5), f64),
+                           ("status", out["status"], (B,), i32), ("iters", out["iters"], (B,), i32), ("tick", tick, (B,), i64),
+                           ("phase", phase, (B,), i32), ("U_last", U_last, (B, N, 5), f64), ("u0", u0, (B, T, 5), f64),
+                           ("iters_hist", iters_hist, (B, T), i32), ("status_hist", status_hist, (B, T), i32),
+                           ("phase_hist", phase_hist, (B, T), i32), ("counters", counters, (4,), i32)), names, dev)
+        if U_last.data_ptr() == out["U"].data_ptr():
+            raise ValueError("U_last must not be out['U']")
+        st = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
+        p = lambda t_: C.c_void_p(t_.data_ptr())
+        self._chk(lib().mmpc_mission_commit_device(self._h, B, p(hold), p(solve_phase), int(set), int(rejoin), p(out["U"]), p(out["status"]),
+                                                   p(out["iters"]), p(tick), p(phase), p(U_last), p(u0), p(iters_hist), p(status_hist),
+                                                   p(phase_hist), int(T), p(counters), C.c_void_p(st)), "mmpc_mission_commit_device")

@@ -22,6 +22,7 @@
 #include "mmpc_tick.h"
 #include "mmpc_mission.h"
 #include "mmpc_manipulate.h"
+#include "mmpc_round.h"
 #include "mmpc_guess.h"
 
 template <int KIND, int NC = 0, int MC = -1, int OPSC = -1, int LC = -1>
@@ -1177,6 +1178,140 @@ extern "C" int mmpc_shift_guess_device(mmpc_handle h, int B, const int *d_phase,
     hipStream_t st = (hipStream_t)stream;
     if (h->ev_valid && st != h->last_stream) HIPCHK(h, hipStreamWaitEvent(st, h->ev, 0));
     hipLaunchKernelGGL(mmpc_guess_kernel, dim3(B), dim3(MMPC_WAVE), 0, st, h->dp, B, d_phase, d_U_prev, d_x_in, d_u_guess, d_x_guess);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipEventRecord(h->ev, st));
+    h->ev_valid = 1; h->last_stream = st;
+    return MMPC_OK;
+}
+
+// ---- missions under iteration budgets (mmpc_round.h): the mission and manipulate kernels per robot under a hold word, and the commit
+__global__ __launch_bounds__(MMPC_WAVE) void mmpc_mission_round_kernel(
+    const MmpcParams *__restrict__ Pp, int B, double *__restrict__ x, long long *__restrict__ tick, int *__restrict__ phase,
+    const double *__restrict__ U_last, const double *__restrict__ glob, int nglob, const double *__restrict__ obs0,
+    const double *__restrict__ vel, double *__restrict__ x_in, double *__restrict__ traj_ref, int *__restrict__ start,
+    double *__restrict__ obs, int *__restrict__ lists, int *__restrict__ counts, int *__restrict__ hold, int *__restrict__ solve_phase,
+    long long tick_limit) {
+    __shared__ double lds[MMPC_TICK_LDS];
+    __shared__ int spare[MMPC_ROUND_SPARE];
+    const int b = (int)blockIdx.x;
+    if (b >= B) return;
+    mmpc_mission_round_robot(*Pp, b, B, x, tick, phase, U_last, glob, nglob, obs0, vel, x_in, traj_ref, start, obs, lists, counts, hold,
+                             solve_phase, tick_limit, lds, spare);
+}
+
+// the checks mmpc_mission_round_device and mmpc_manipulate_round_device share with the prepare calls (nullptr: fine)
+static const char *round_bad(mmpc_handle h, int B, const double *d_x, const long long *d_tick, const int *d_phase, const double *d_U_last,
+                             const double *d_obs0, const double *d_vel, const double *d_obs, const int *d_hold, const int *d_solve_phase,
+                             long long tick_limit) {
+    if (B < 1 || B > h->cfg.max_batch) return "B must be in 0..max_batch";
+    if (!d_x || !d_tick || !d_phase) return "d_x, d_tick and d_phase are required";
+    if (!d_U_last || !d_hold || !d_solve_phase) return "d_U_last, d_hold and d_solve_phase are required";
+    if (tick_limit < 1) return "tick_limit must be at least 1";
+    if (d_obs && h->cfg.M > 0 && (!d_obs0 || !d_vel)) return "the obstacle table needs d_obs0 and d_vel";
+    return nullptr;
+}
+
+extern "C" int mmpc_mission_round_device(mmpc_handle h, int B, double *d_x, long long *d_tick, int *d_phase, const double *d_U_last,
+                                         const double *d_glob, int nglob, const double *d_obs0, const double *d_vel, double *d_x_in,
+                                         double *d_traj_ref, int *d_start, double *d_obs, int *d_lists, int *d_counts, int *d_hold,
+                                         int *d_solve_phase, long long tick_limit, void *stream) {
+    if (!h) return MMPC_E_ARG;
+    if (h->cfg.kind != MMPC_KIND_WHOLEBODY || !h->hp.obs_per_stage)
+        return fail(h, MMPC_E_UNSUPPORTED, "mmpc_mission_round_device: %s%s", "needs a whole-body handle (joint-space reference) created with obs_per_stage = 1 or 2");
+    if (h->hp.obs_per_stage == 2 && d_obs)
+        return fail(h, MMPC_E_ARG, "mmpc_mission_round_device: %s%s", "d_obs must be NULL on a motion handle (obs_per_stage = 2): the kernels form the centres from the record and the clock");
+    if (B == 0) return MMPC_OK;
+    if (const char *why = round_bad(h, B, d_x, d_tick, d_phase, d_U_last, d_obs0, d_vel, d_obs, d_hold, d_solve_phase, tick_limit))
+        return fail(h, MMPC_E_ARG, "mmpc_mission_round_device: %s%s", why);
+    if (!d_lists || !d_counts) return fail(h, MMPC_E_ARG, "mmpc_mission_round_device: %s%s", "d_lists and d_counts are required");
+    if (!d_glob || nglob < 1 || nglob > (1 << 24)) return fail(h, MMPC_E_ARG, "mmpc_mission_round_device: %s%s", "d_glob is required, nglob must be in 1..2^24");
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    hipStream_t st = (hipStream_t)stream;
+    if (h->ev_valid && st != h->last_stream) HIPCHK(h, hipStreamWaitEvent(st, h->ev, 0));
+    HIPCHK(h, hipMemsetAsync(d_counts, 0, 4 * sizeof(int), st));
+    hipLaunchKernelGGL(mmpc_mission_round_kernel, dim3(B), dim3(MMPC_WAVE), 0, st, h->dp, B, d_x, d_tick, d_phase, d_U_last, d_glob, nglob,
+                       d_obs0, d_vel, d_x_in, d_traj_ref, d_start, d_obs, d_lists, d_counts, d_hold, d_solve_phase, tick_limit);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipEventRecord(h->ev, st));
+    h->ev_valid = 1; h->last_stream = st;
+    return MMPC_OK;
+}
+
+__global__ __launch_bounds__(MMPC_WAVE) void mmpc_manipulate_round_kernel(
+    const MmpcParams *__restrict__ Pp, int B, double *__restrict__ x, long long *__restrict__ tick, int *__restrict__ phase,
+    const double *__restrict__ U_last, const double *__restrict__ pose, int nplan, double *plan, double *__restrict__ qgoal,
+    int *__restrict__ ik_status, const double *__restrict__ obs0, const double *__restrict__ vel, double *__restrict__ x_in,
+    double *__restrict__ traj_ref, int *__restrict__ start, double *__restrict__ obs, int *__restrict__ list, int *__restrict__ counts,
+    int *__restrict__ hold, int *__restrict__ solve_phase, long long tick_limit) {
+    __shared__ double lds[MMPC_TICK_LDS];
+    __shared__ int spare[MMPC_ROUND_SPARE];
+    const int b = (int)blockIdx.x;
+    if (b >= B) return;
+    mmpc_manipulate_round_robot(*Pp, b, B, x, tick, phase, U_last, pose, nplan, plan, qgoal, ik_status, obs0, vel, x_in, traj_ref, start, obs,
+                                list, counts, hold, solve_phase, tick_limit, lds, spare);
+}
+
+extern "C" int mmpc_manipulate_round_device(mmpc_handle h, int B, double *d_x, long long *d_tick, int *d_phase, const double *d_U_last,
+                                            const double *d_pose, int nplan, double *d_plan, double *d_qgoal, int *d_ik_status,
+                                            const double *d_obs0, const double *d_vel, double *d_x_in, double *d_traj_ref, int *d_start,
+                                            double *d_obs, int *d_list, int *d_counts, int *d_hold, int *d_solve_phase,
+                                            long long tick_limit, void *stream) {
+    if (!h) return MMPC_E_ARG;
+    if (h->cfg.kind != MMPC_KIND_WHOLEBODY || !h->hp.obs_per_stage)
+        return fail(h, MMPC_E_UNSUPPORTED, "mmpc_manipulate_round_device: %s%s", "needs a whole-body handle (joint-space reference) created with obs_per_stage = 1 or 2");
+    if (h->hp.obs_per_stage == 2 && d_obs)
+        return fail(h, MMPC_E_ARG, "mmpc_manipulate_round_device: %s%s", "d_obs must be NULL on a motion handle (obs_per_stage = 2): the kernels form the centres from the record and the clock");
+    if (B == 0) return MMPC_OK;
+    if (const char *why = round_bad(h, B, d_x, d_tick, d_phase, d_U_last, d_obs0, d_vel, d_obs, d_hold, d_solve_phase, tick_limit))
+        return fail(h, MMPC_E_ARG, "mmpc_manipulate_round_device: %s%s", why);
+    if (!d_pose || !d_plan || !d_list || !d_counts)
+        return fail(h, MMPC_E_ARG, "mmpc_manipulate_round_device: %s%s", "d_pose, d_plan, d_list and d_counts are required");
+    if (nplan < 2 || nplan > (1 << 16)) return fail(h, MMPC_E_ARG, "mmpc_manipulate_round_device: %s%s", "nplan must be in 2..2^16");
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    hipStream_t st = (hipStream_t)stream;
+    if (h->ev_valid && st != h->last_stream) HIPCHK(h, hipStreamWaitEvent(st, h->ev, 0));
+    HIPCHK(h, hipMemsetAsync(d_counts, 0, 2 * sizeof(int), st));
+    hipLaunchKernelGGL(mmpc_manipulate_round_kernel, dim3(B), dim3(MMPC_WAVE), 0, st, h->dp, B, d_x, d_tick, d_phase, d_U_last, d_pose, nplan,
+                       d_plan, d_qgoal, d_ik_status, d_obs0, d_vel, d_x_in, d_traj_ref, d_start, d_obs, d_list, d_counts, d_hold, d_solve_phase,
+                       tick_limit);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipEventRecord(h->ev, st));
+    h->ev_valid = 1; h->last_stream = st;
+    return MMPC_OK;
+}
+
+__global__ __launch_bounds__(MMPC_WAVE) void mmpc_commit_kernel(
+    int N, int B, int *__restrict__ hold, int *__restrict__ solve_phase, int set, int rejoin, const double *__restrict__ U,
+    const int *__restrict__ status, const int *__restrict__ iters, const long long *__restrict__ tick, const int *__restrict__ phase,
+    double *__restrict__ U_last, double *__restrict__ u0, int *__restrict__ iters_hist, int *__restrict__ status_hist,
+    int *__restrict__ phase_hist, int T, int *__restrict__ counters) {
+    const int b = (int)blockIdx.x;
+    if (b >= B) return;
+    mmpc_commit_robot(N, b, hold, solve_phase, set, rejoin, U, status, iters, tick, phase, U_last, u0, iters_hist, status_hist, phase_hist,
+                      T, counters);
+}
+
+extern "C" int mmpc_mission_commit_device(mmpc_handle h, int B, int *d_hold, int *d_solve_phase, int set, int rejoin, const double *d_U,
+                                          const int *d_status, const int *d_iters, const long long *d_tick, const int *d_phase,
+                                          double *d_U_last, double *d_u0, int *d_iters_hist, int *d_status_hist, int *d_phase_hist, int T,
+                                          int *d_counters, void *stream) {
+    if (!h) return MMPC_E_ARG;
+    if (h->cfg.kind != MMPC_KIND_WHOLEBODY)
+        return fail(h, MMPC_E_UNSUPPORTED, "mmpc_mission_commit_device: %s%s", "needs a whole-body handle (joint-space reference)");
+    if (B == 0) return MMPC_OK;
+    if (B < 1 || B > h->cfg.max_batch) return fail(h, MMPC_E_ARG, "mmpc_mission_commit_device: %s%s", "B must be in 0..max_batch");
+    if (!d_hold || !d_solve_phase || !d_U || !d_status || !d_iters || !d_tick || !d_phase || !d_U_last || !d_u0 || !d_iters_hist ||
+        !d_status_hist || !d_phase_hist || !d_counters)
+        return fail(h, MMPC_E_ARG, "mmpc_mission_commit_device: %s%s", "every array is required");
+    if (d_U_last == d_U) return fail(h, MMPC_E_ARG, "mmpc_mission_commit_device: %s%s", "d_U_last must not be d_U");
+    if (set < 0 || set > 15 || (rejoin != 0 && rejoin != 1) || T < 1)
+        return fail(h, MMPC_E_ARG, "mmpc_mission_commit_device: %s%s", "set must be in 0..15, rejoin 0 or 1, T at least 1");
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    hipStream_t st = (hipStream_t)stream;
+    if (h->ev_valid && st != h->last_stream) HIPCHK(h, hipStreamWaitEvent(st, h->ev, 0));
+    HIPCHK(h, hipMemsetAsync(d_counters, 0, 4 * sizeof(int), st));
+    hipLaunchKernelGGL(mmpc_commit_kernel, dim3(B), dim3(MMPC_WAVE), 0, st, h->cfg.N, B, d_hold, d_solve_phase, set, rejoin, d_U, d_status,
+                       d_iters, d_tick, d_phase, d_U_last, d_u0, d_iters_hist, d_status_hist, d_phase_hist, T, d_counters);
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipEventRecord(h->ev, st));
     h->ev_valid = 1; h->last_stream = st;

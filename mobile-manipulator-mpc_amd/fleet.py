@@ -53,8 +53,15 @@ also gives it iteration budgets, and with them run_async.  True builds a missing
 generic_budget=True: every handle of the fleet (sub-fleets of run_groups, the handles of run_async and the mission handles included)
 is created with mmpc_config.generic_budget: iteration budgets and continuation also where a handle runs the generic kernel.  run_async
 then works at an unlisted (N, M) without a shape library - no hipcc run -, with the per-robot results of run_lockstep bit for bit.  The
-handles run the run-time-sized generic kernel (not the static-LDS instantiation of a listed configuration).  Missions are not part of
-run_async: run_mission sets no budget.
+handles run the run-time-sized generic kernel (not the static-LDS instantiation of a listed configuration).
+
+run_mission(..., budget=b, sets=k) on such a fleet: the mission under iteration budgets.  A tick of the lock step lasts as long as its
+slowest solve; here a solve that uses up its b iterations is continued on a side stream and its robot rejoins k rounds later, one or
+more ticks behind, while every other robot goes on.  The glue between two solves is per robot and stays on the device: a hold word
+per robot (MMPC_HOLD_*), the mission and manipulate kernels under it (mmpc_mission_round_device, mmpc_manipulate_round_device), and a
+commit kernel that takes a round's solves into U_last and the per-tick histories (mmpc_mission_commit_device; csrc/mmpc_round.h).
+k groups of budgeted phase handles alternate; the per-robot results are those of run_mission without a budget, bit for bit.  The
+default stays budget=0.  Not built: mmpc_resume_batch_device runs to the end, so a 2 000-iteration solve still holds its handle set.
 """
 import numpy as np
 
@@ -254,7 +261,31 @@ class DeviceFleet:
             self._mission_ctrls.append(man)
         return [c._engine for c in self._mission_ctrls[:4 if manipulate else 3]]
 
-    def run_mission(self, T, streams=3, on_tick=None, manipulate=None, warm_start="reference"):
+    def _mission_set_handles(self, sets, manipulate=False):
+        """The handles of a mission under a budget: `sets` groups of [move, approach, rotate(, manipulate)], each group the
+        controller states of _mission_handles on controllers of its own (a continuation belongs to the budgeted launch directly before
+        it on its handle, so a group is not launched on again before its continuations are back; the lock-step handle runs the glue
+        and no solve).  In motion mode every handle reads the lock-step clock: a held robot's tick does not move."""
+        if not hasattr(self, "_mission_sets"):
+            self._mission_sets = []
+        N = self.N
+        while len(self._mission_sets) < sets:
+            self._mission_sets.append([])
+        for grp in self._mission_sets[:sets]:
+            while len(grp) < (4 if manipulate else 3):
+                p = len(grp)
+                c = self._mk()
+                if p >= 1:
+                    c.opti.subject_to(c.X[N, :2] == c.X_ref[N, :2])
+                if p >= 2:
+                    W = np.diag([5, 5, 5, 0, 0, 1, 1, 1, 1] if p == 2 else [500, 500, 500, 0, 0, 1, 1, 1, 1])
+                    c.setWeight(P=W, Q=W)
+                if self.motion:
+                    c._engine.set_obstacle_clock(self._clock0)
+                grp.append(c)
+        return [[c._engine for c in grp[:4 if manipulate else 3]] for grp in self._mission_sets[:sets]]
+
+    def run_mission(self, T, streams=3, on_tick=None, manipulate=None, warm_start="reference", budget=0, sets=2, max_rounds=None, on_round=None):
         """T mission ticks.  streams=1: everything on the current stream; streams=3 (default: 0.5 % faster at B = 8192,
         profiles/fleet_mission.txt): the three list launches of a tick on three streams, forked after the mission kernel and joined
         before the next one; the results are bitwise the same.  Returns u0 (B,T,5), iters, status (B,T) - zero
@@ -277,8 +308,35 @@ class DeviceFleet:
         list launch starts there and every handle of the mission runs with mu_0 = 0.1 (set at tick 1 - each handle waits once for its
         launches in flight, the only host waits of a run - and put back when the run ends, also when on_tick raises).  u_last stays
         the previous optimum, so the NLP of every tick is the same; the returned dict has the same entries; on_tick also gets u_guess
-        and x_guess (meaningful from tick 1 on, in the rows of the robots solved at that tick)."""
+        and x_guess (meaningful from tick 1 on, in the rows of the robots solved at that tick).
+        budget=0 (default): the lock step above, unchanged.  budget > 0 (needs a fleet constructed with generic_budget=True; no
+        on_tick; `streams` is not used): every list launch gives a solve at most `budget` iterations.  A robot whose solve uses it up is
+        continued on a side stream (mmpc_resume_batch_device) and rejoins `sets` rounds later, one or more ticks behind; every other
+        robot goes on.  Round r runs on handle set r % sets (sets in 2..4, _mission_set_handles): commit of the set's continuations
+        that are back (mmpc_mission_commit_device, rejoin), the mission and manipulate kernels per robot under a hold word
+        (mmpc_mission_round_device, mmpc_manipulate_round_device: csrc/mmpc_round.h), the guess kernel on the robots the round solves,
+        the list launches, their commit, and the set's continuations on side streams of their own.  All glue runs on the lock-step
+        handle, which solves nothing here.  One input set and one output set serve every handle set: the rows of a held robot are
+        written by nobody but its continuation.  Robots do not interact, so every number a robot produces is the lock step's, bit
+        for bit, indexed by the robot's own tick; phase[b][t] of a tick after a robot froze is its frozen code, counts and mcounts are
+        formed from the phase history and equal the lock step's.  The loop ends when no robot has work left (the commit kernel's live
+        counter, read on the host from round T on) or after max_rounds (default (sets + 2) T + 8) rounds - then all_converged is
+        false.  shifted: set 0 is cold in round 0; every set gets mu_0 = 0.1 before its first warm round (a host wait per handle).
+        Returned in addition: rounds, and suspended - the number of solves that used up their budget.  on_round(r, s): called after
+        round r is queued, on the main stream, with the tensors counts (4,), counters (4,) = committed, suspended, failed, live of the
+        round's commit and, with manipulate, mcounts (2,); the next round rewrites them, so a caller that keeps them clones them."""
         torch = self.torch
+        if budget < 0:
+            raise ValueError("budget must be >= 0, not %r" % (budget,))
+        if sets not in (2, 3, 4):
+            raise ValueError("sets must be 2, 3 or 4, not %r" % (sets,))
+        if budget > 0 and not self.generic_budget:
+            raise ValueError("run_mission(budget=...) needs a fleet constructed with generic_budget=True: the approach, rotate and "
+                             "manipulate handles run the generic kernel, which takes a budget only then")
+        if budget == 0 and on_round is not None:
+            raise ValueError("on_round belongs to a run under a budget; the lock step calls on_tick")
+        if budget > 0 and on_tick is not None:
+            raise ValueError("on_tick has no meaning under a budget: the robots of a round are at different ticks (use budget=0)")
         if self.warm_start != "reference":
             raise ValueError("a fleet constructed with warm_start='shifted' runs its lock step that way; a mission takes the switch as "
                              "its own keyword: run_mission(..., warm_start='shifted') on a fleet constructed with the default")
@@ -300,7 +358,7 @@ class DeviceFleet:
             nplan = int(t_man / self.dt) + 1
             if nplan > 1 << 16:
                 raise ValueError("manipulate['t_manipulate'] gives a plan of %d rows; at most 65536" % nplan)
-        engs = self._mission_handles(manip)
+        engs = self._mission_handles(manip) if budget == 0 else None
         f64, i32 = self.f64, dict(dtype=torch.int32, device=dev)
         if not hasattr(self, "_msets"):
             mkout = lambda: dict(X=torch.zeros((B, N + 1, 9), **f64), U=torch.zeros((B, N, 5), **f64), s=torch.zeros((B, N + 1), **f64),
@@ -324,6 +382,8 @@ class DeviceFleet:
             G["pose"].copy_(torch.from_numpy(pose)); G["plan"].zero_(); G["qgoal"].zero_(); G["ik_status"].fill_(-1)
             mcnts = torch.zeros((T, 2), **i32)
             mkw = dict(pose=G["pose"], plan=G["plan"], lst=G["list"], counts=G["counts"], qgoal=G["qgoal"], ik_status=G["ik_status"])
+        if budget > 0:
+            return self._mission_rounds(T, int(budget), sets, max_rounds, shifted, F, G if manip else None, mkw if manip else None, on_round)
         for e in engs:
             e.set_iteration_budget(0); e.reset()
         x = self.x0.clone()
@@ -385,6 +445,104 @@ class DeviceFleet:
         res = dict(u0=hist, iters=its, status=sts, phase=phs, counts=cnts, x=x, final_phase=phase.clone(), all_converged=(sts == 0).all(), rounds=T)
         if manip:
             res.update(mcounts=mcnts, qgoal=G["qgoal"].clone(), ik_status=G["ik_status"].clone(), plan=G["plan"].clone())
+        return res
+
+    def _mission_rounds(self, T, budget, sets, max_rounds, shifted, F, G, mkw, on_round=None):
+        """run_mission under a budget (its docstring): F, G the input buffers and the manipulate state run_mission has set up."""
+        torch = self.torch
+        B, N = self.B, self.N
+        dev = self.dev
+        manip = G is not None
+        f64, i32 = self.f64, dict(dtype=torch.int32, device=dev)
+        glue = self.engs[0]
+        groups = self._mission_set_handles(sets, manip)
+        if not hasattr(self, "_mround"):
+            self._mround = dict(U_last=torch.zeros((B, N, 5), **f64), hold=torch.zeros(B, **i32), solve_phase=torch.zeros(B, **i32),
+                                counters=torch.zeros(4, **i32), sides=[])
+        R = self._mround
+        while len(R["sides"]) < sets:
+            R["sides"].append([])
+        for sd in R["sides"][:sets]:
+            while len(sd) < len(groups[0]):
+                sd.append(torch.cuda.Stream(device=dev))
+        out = self._msets[0]
+        for grp in groups:
+            for e in grp:
+                e.set_iteration_budget(budget); e.reset()
+        x = self.x0.clone()
+        tick = self._clock0.zero_()[:B] if self.motion else torch.zeros(B, dtype=torch.int64, device=dev)
+        phase, lists, counts = F["phase"].zero_(), F["lists"], F["counts"]
+        hold, sp, U_last, counters = R["hold"].zero_(), R["solve_phase"].fill_(-1), R["U_last"].zero_(), R["counters"]
+        tab = dict() if self.motion else dict(obs0=self.obs0, vel=self.vel, obs=F["obs"])
+        ug, xg = (F["ug"], F["xg"]) if shifted else (None, None)
+        hist = torch.zeros((B, T, 5), **f64)
+        its, sts, phs = torch.zeros((B, T), **i32), torch.zeros((B, T), **i32), torch.full((B, T), -1, **i32)
+        nsusp = torch.zeros((), dtype=torch.int64, device=dev)
+        main = torch.cuda.current_stream(dev)
+        back = [None] * sets                 # per set: the events of its continuations in flight
+        warm_set = [False] * sets
+        cap = max_rounds if max_rounds is not None else (sets + 2) * T + 8
+        commit = lambda s, rejoin: glue.mission_commit(hold, sp, s, rejoin, out, tick, phase, U_last, hist, its, sts, phs, counters)
+        r, live = 0, -1
+        try:
+            while True:
+                s = r % sets
+                engs = groups[s]
+                if back[s] is not None:
+                    # the continuations of round r - sets (same handles) are finished: their robots rejoin
+                    for ev in back[s]:
+                        main.wait_event(ev)
+                    back[s] = None
+                    commit(s, 1)
+                glue.mission_round(x, tick, phase, lists, counts, U_last, hold, sp, T, glob=self.glob, x_in=F["x_in"], traj_ref=F["loc"], **tab)
+                if manip:
+                    glue.manipulate_round(x, tick, phase, U_last=U_last, hold=hold, solve_phase=sp, tick_limit=T, x_in=F["x_in"],
+                                          traj_ref=F["loc"], **mkw, **tab)
+                warm = shifted and r >= 1        # (only round 0 solves robots that have no optimum yet)
+                if warm:
+                    glue.shift_guess(sp, U_last, F["x_in"], ug, xg)
+                    if not warm_set[s]:
+                        for e in engs:
+                            e.set_warm_start(ug, 0.1)        # (waits for the handle's launches in flight)
+                        warm_set[s] = True
+                kw = dict(x_guess=xg) if warm else {}
+                for p, e in enumerate(engs):
+                    rows = (lists[p], counts[p:p + 1]) if p < 3 else (G["list"], G["counts"][0:1])
+                    e.solve_rows_device(rows, F["x_in"], F["loc"], self.uref, U_last, F["obs"], out, **kw)
+                commit(s, 0)
+                nsusp += counters[1]
+                ev = torch.cuda.Event(); ev.record(main)
+                back[s] = []
+                for p, e in enumerate(engs):
+                    side = R["sides"][s][p]
+                    side.wait_event(ev)
+                    e.resume_batch_device(F["x_in"], F["loc"], self.uref, U_last, F["obs"], out, stream=side.cuda_stream, **kw)
+                    evp = torch.cuda.Event(); evp.record(side)
+                    back[s].append(evp)
+                if on_round is not None:
+                    on_round(r, dict(counts=counts, counters=counters, **(dict(mcounts=G["counts"]) if manip else {})))
+                r += 1
+                if r >= T:
+                    live = int(counters[3])
+                    if live == 0 or r >= cap:
+                        break
+        finally:
+            for s in range(sets):
+                for ev in back[s] or ():
+                    ev.synchronize()
+                for e in groups[s]:
+                    e.set_iteration_budget(0)
+                    if warm_set[s]:
+                        e.set_warm_start(None, 1.0)
+        final = phase.clone()
+        phs = torch.where(phs < 0, final[:, None], phs)          # a tick after a robot froze: its frozen code
+        drive = torch.stack([(phs == p).sum(dim=0) for p in range(3)], dim=1).to(torch.int32)
+        cnts = torch.cat([drive, (B - drive.sum(dim=1, keepdim=True)).to(torch.int32)], dim=1)
+        res = dict(u0=hist, iters=its, status=sts, phase=phs, counts=cnts, x=x, final_phase=final,
+                   all_converged=(sts == 0).all() & torch.tensor(live == 0, device=dev), rounds=r, suspended=int(nsusp))
+        if manip:
+            res.update(mcounts=torch.stack([(phs == 4).sum(dim=0), (phs == 5).sum(dim=0)], dim=1).to(torch.int32), qgoal=G["qgoal"].clone(),
+                       ik_status=G["ik_status"].clone(), plan=G["plan"].clone())
         return res
 
     # ---- groups in lock step, out of phase
