@@ -277,6 +277,27 @@ int mmpc_resume_batch_device(mmpc_handle h, int B, const double *d_x_init, const
                              double *d_s, int *d_status, int *d_iters, double *d_cost, double *d_err, void *stream);
 int mmpc_suspended_count(mmpc_handle h, int *count);
 
+/* Resume budget: a continuation that can be suspended again (opt-in; c = 0, the default, is everything above unchanged).  c < 0:
+ * MMPC_E_ARG; c > 0 on a handle that takes no iteration budget: MMPC_E_UNSUPPORTED, as mmpc_set_iteration_budget.  Waits for the
+ * handle's launches in flight; does not invalidate a pending continuation (a solve is the same bits wherever it is cut).  With c > 0:
+ *   - mmpc_resume_batch_device gives every suspended instance at most c further iterations (same striding grid).  An instance that is
+ *     still unfinished keeps status 3, its iters is the total so far, X/U/s hold the current iterate and its save area is rewritten;
+ *     one that reaches max_iter inside the continuation ends with status 1 (the cap comes first, as in a budgeted launch).  After the
+ *     kernel, on the same stream, the handle's list is compacted to the instances whose status is still 3, and the continuation
+ *     stays valid: another mmpc_resume_batch_device with the same B and the same arguments continues exactly those, and so on; with
+ *     nobody left it is a no-op that returns MMPC_OK.  mmpc_suspended_count: the count after the latest budgeted launch or
+ *     continuation.
+ *   - A budgeted list launch (mmpc_solve_list_device, mmpc_solve_rows_device) that could have been a continuation - same B, same
+ *     kernel family, none of the events above in between - keeps the handle's suspended set S and merges: S := {b in S :
+ *     status[b] == 3} united with {b listed : status[b] == 3}, every row once (also where the list names a row twice).  A carried row
+ *     that the list names again starts afresh: the launch overwrites its save area, and it is in S by its new status.  The caller
+ *     passes the same output buffers, and unchanged inputs for the carried rows ("same arguments as the launch it continues").
+ *     A whole-batch budgeted launch replaces S as before.
+ *   - The continuation inside the host-pointer mmpc_solve_batch runs to the end whatever c is: that call returns finished solves.
+ * The two list buffers and the duplicate guard of the merge (a stamp per row) are allocated with the save areas, at the first
+ * budget; no launch gains a host synchronisation, an allocation or a copy (csrc/mmpc_suspend.h). */
+int mmpc_set_resume_budget(mmpc_handle h, int c);
+
 /* The glue of one receding-horizon tick for B robots that stay in device memory between ticks (no reference counterpart as
  * a batch; per robot it is the reference's closed loop without the simulator, interface_wholebody_qref.py:100-143).  Whole-body
  * handles created with obs_per_stage = 1 or 2 only (MMPC_E_UNSUPPORTED otherwise); N, M, dt and xlim come from the handle.  One
@@ -404,7 +425,8 @@ int mmpc_shift_guess_device(mmpc_handle h, int B, const int *d_phase, const doub
  * A round of a mission under budgets is: mmpc_mission_commit_device(rejoin = 1) for the handle set whose continuations have come
  * back; this call; mmpc_manipulate_round_device when the phase is on; mmpc_shift_guess_device with d_solve_phase as d_phase and
  * d_U_last as d_U_prev (shifted warm start); mmpc_solve_rows_device on the budgeted handles of the set with d_u_last = d_U_last;
- * mmpc_mission_commit_device(rejoin = 0); mmpc_resume_batch_device per handle on side streams (fleet.py:DeviceFleet.run_mission). */
+ * mmpc_mission_commit_device(rejoin = 0); mmpc_resume_batch_device per handle on side streams (fleet.py:DeviceFleet.run_mission).
+ * With a resume budget on the set's handles (mmpc_set_resume_budget) mmpc_mission_rejoin_device takes the place of the first call. */
 int mmpc_mission_round_device(mmpc_handle h, int B, double *d_x, long long *d_tick, int *d_phase, const double *d_U_last,
                               const double *d_glob, int nglob, const double *d_obs0, const double *d_vel, double *d_x_in,
                               double *d_traj_ref, int *d_start, double *d_obs, int *d_lists, int *d_counts, int *d_hold,
@@ -445,6 +467,18 @@ int mmpc_mission_commit_device(mmpc_handle h, int B, int *d_hold, int *d_solve_p
                                const int *d_status, const int *d_iters, const long long *d_tick, const int *d_phase, double *d_U_last,
                                double *d_u0, int *d_iters_hist, int *d_status_hist, int *d_phase_hist, int T, int *d_counters,
                                void *stream);
+
+/* The rejoin of a run whose continuations can be suspended again (mmpc_set_resume_budget): the arguments of
+ * mmpc_mission_commit_device without rejoin, the same argument checks, hipMemsetAsync of the counters and stream ordering.  Handles
+ * the robots with d_hold[b] == SUSPENDED + set:
+ *   - d_status[b] == 3 (the continuation used up its resume budget): the robot stays SUSPENDED + set, nothing of it is written, and
+ *     counters[1] += 1;
+ *   - any other status: exactly what mmpc_mission_commit_device(rejoin = 1) does - d_U_last, the histories at d_tick[b], hold READY,
+ *     counters[0], and counters[2] on a failed status.
+ * counters[3] counts the live robots as there.  In a round it takes the place of mmpc_mission_commit_device(rejoin = 1). */
+int mmpc_mission_rejoin_device(mmpc_handle h, int B, int *d_hold, int *d_solve_phase, int set, const double *d_U, const int *d_status,
+                               const int *d_iters, const long long *d_tick, const int *d_phase, double *d_U_last, double *d_u0,
+                               int *d_iters_hist, int *d_status_hist, int *d_phase_hist, int T, int *d_counters, void *stream);
 
 /* Streams and threads: a handle owns device state that its launches read and write (parameter block, schedule hint,
  * warm start).  Calls on one handle must come from one host thread at a time.  Launches may use different streams:

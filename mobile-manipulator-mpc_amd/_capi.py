@@ -31,6 +31,7 @@ EXPORTS = ["mmpc_create", "mmpc_destroy", "mmpc_set_weights", "mmpc_set_terminal
            "mmpc_tick_prepare_device", "mmpc_set_obstacle_clock", "mmpc_set_objective_scaling",
            "mmpc_mission_prepare_device", "mmpc_manipulate_prepare_device", "mmpc_solve_rows_device", "mmpc_shift_guess_device",
            "mmpc_mission_round_device", "mmpc_manipulate_round_device", "mmpc_mission_commit_device",
+           "mmpc_set_resume_budget", "mmpc_mission_rejoin_device",
            "mmpc_shape_supported", "mmpc_load_shape_library", "mmpc_runs_specialised", "mmpc_set_persistent_grid"]
 LISTED_SHAPES = ((KIND_WHOLEBODY, 20, 5), (KIND_WHOLEBODY, 30, 8), (KIND_WHOLEBODY, 20, 3), (KIND_BASE, 15, 3))   # MMPC_FAST_LIST
 
@@ -85,6 +86,8 @@ def lib():
         L.mmpc_mission_round_device.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 5 + [C.c_int] + [C.c_void_p] * 10 + [C.c_longlong, C.c_void_p]
         L.mmpc_manipulate_round_device.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 5 + [C.c_int] + [C.c_void_p] * 13 + [C.c_longlong, C.c_void_p]
         L.mmpc_mission_commit_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 10 + [C.c_int, C.c_void_p, C.c_void_p]
+        L.mmpc_mission_rejoin_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 10 + [C.c_int, C.c_void_p, C.c_void_p]
+        L.mmpc_set_resume_budget.argtypes = [C.c_void_p, C.c_int]
         L.mmpc_solve_rows_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 13 + [C.c_void_p]
         L.mmpc_set_obstacle_clock.argtypes = [C.c_void_p, C.c_void_p]
         L.mmpc_set_objective_scaling.argtypes = [C.c_void_p, C.c_double, C.c_void_p]
@@ -180,7 +183,7 @@ class Engine:
         self.nref = 4 if kind == KIND_WHOLEBODY_POSE else self.nx      # reference row: endpoint pose (x,y,z,psi) or the state
         # obs_per_stage: False (static record), True (table per stage), "motion" (record with velocities + clock); an int is
         # handed to mmpc_create as it is (which refuses anything but 0, 1, 2)
-        self.max_batch, self.device = int(max_batch), int(device)
+        self.max_batch, self.device, self.max_iter = int(max_batch), int(device), int(max_iter)
         self.obs_mode = 2 if obs_per_stage == "motion" else int(obs_per_stage)
         self.obs_per_stage = "motion" if self.obs_mode == 2 else bool(self.obs_mode)
         cfg = MmpcConfig()
@@ -321,8 +324,15 @@ class Engine:
         specialised kernel for the shape, or an engine created with generic_budget."""
         self._chk(lib().mmpc_set_iteration_budget(self._h, int(budget)), "mmpc_set_iteration_budget")
 
+    def set_resume_budget(self, c):
+        """mmpc_set_resume_budget: iterations a continuation may spend on a suspended instance before it is suspended again (0, the
+        default: resume_batch_device runs to the end).  With c > 0 resume_batch_device can be called again until suspended_count()
+        is 0, and a budgeted list launch carries the instances that are still suspended."""
+        self._chk(lib().mmpc_set_resume_budget(self._h, int(c)), "mmpc_set_resume_budget")
+
     def suspended_count(self):
-        """mmpc_suspended_count: instances the last budgeted launch left suspended (waits for the handle's launches)."""
+        """mmpc_suspended_count: instances the last budgeted launch - or, under a resume budget, the last continuation - left
+        suspended (waits for the handle's launches)."""
         n = C.c_int(0)
         self._chk(lib().mmpc_suspended_count(self._h, C.byref(n)), "mmpc_suspended_count")
         return n.value
@@ -616,6 +626,15 @@ class Engine:
         (rejoin = 0) or HOLD_SUSPENDED + set (rejoin = 1), which become HOLD_READY - or, with status 3 and rejoin = 0, HOLD_SUSPENDED +
         set.  counters (4,) int32 = committed, suspended, failed, live (over all robots).  Asynchronous on torch's current stream (or
         `stream`)."""
+        self._commit_call(hold, solve_phase, set, int(rejoin), out, tick, phase, U_last, u0, iters_hist, status_hist, phase_hist, counters, stream)
+
+    def mission_rejoin(self, hold, solve_phase, set, out, tick, phase, U_last, u0, iters_hist, status_hist, phase_hist, counters, stream=None):
+        """mmpc_mission_rejoin_device: mission_commit(rejoin = 1) for a run under a resume budget - a robot with HOLD_SUSPENDED + set
+        whose status is still 3 stays suspended, nothing of it is written and counters[1] counts it; every other one rejoins."""
+        self._commit_call(hold, solve_phase, set, None, out, tick, phase, U_last, u0, iters_hist, status_hist, phase_hist, counters, stream)
+
+    def _commit_call(self, hold, solve_phase, set, rejoin, out, tick, phase, U_last, u0, iters_hist, status_hist, phase_hist, counters, stream):
+        # (rejoin None: mmpc_mission_rejoin_device, which has no such argument)
         import torch
         N = self.N
         B = hold.shape[0]
@@ -632,6 +651,9 @@ class Engine:
             raise ValueError("U_last must not be out['U']")
         st = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
         p = lambda t_: C.c_void_p(t_.data_ptr())
-        self._chk(lib().mmpc_mission_commit_device(self._h, B, p(hold), p(solve_phase), int(set), int(rejoin), p(out["U"]), p(out["status"]),
-                                                   p(out["iters"]), p(tick), p(phase), p(U_last), p(u0), p(iters_hist), p(status_hist),
-                                                   p(phase_hist), int(T), p(counters), C.c_void_p(st)), "mmpc_mission_commit_device")
+        tail = (p(out["U"]), p(out["status"]), p(out["iters"]), p(tick), p(phase), p(U_last), p(u0), p(iters_hist), p(status_hist), p(phase_hist),
+                int(T), p(counters), C.c_void_p(st))
+        if rejoin is None:
+            self._chk(lib().mmpc_mission_rejoin_device(self._h, B, p(hold), p(solve_phase), int(set), *tail), "mmpc_mission_rejoin_device")
+        else:
+            self._chk(lib().mmpc_mission_commit_device(self._h, B, p(hold), p(solve_phase), int(set), int(rejoin), *tail), "mmpc_mission_commit_device")

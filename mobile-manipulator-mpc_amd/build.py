@@ -9,7 +9,7 @@ CSRC = os.path.join(_HERE, "csrc")
 LIB = os.path.join(CSRC, "libmmpc.so")
 SHAPES = os.path.join(CSRC, "shapes")
 SOURCES = ["mmpc_hip.hip"]
-HEADERS = ["mmpc_core.h", "mmpc_tile.h", "mmpc_fast.h", "mmpc_fast_kernel.h", "mmpc_fast_iter.inc", "mmpc_fast_a1r.inc", "mmpc_fast_a1s.inc", "mmpc_fast_d2.inc", "mmpc_ik.h", "mmpc_tick.h", "mmpc_mission.h", "mmpc_manipulate.h", "mmpc_guess.h", "mmpc_round.h", os.path.join("..", "..", "include", "mmpc.h")]
+HEADERS = ["mmpc_core.h", "mmpc_tile.h", "mmpc_fast.h", "mmpc_fast_kernel.h", "mmpc_fast_iter.inc", "mmpc_fast_a1r.inc", "mmpc_fast_a1s.inc", "mmpc_fast_d2.inc", "mmpc_ik.h", "mmpc_tick.h", "mmpc_mission.h", "mmpc_manipulate.h", "mmpc_guess.h", "mmpc_round.h", "mmpc_suspend.h", os.path.join("..", "..", "include", "mmpc.h")]
 SHAPE_SOURCE = "mmpc_shape.hip"
 
 

@@ -12,6 +12,7 @@
 #include <dlfcn.h>
 #include <mutex>
 #include <new>
+#include <utility>
 #include <vector>
 
 #include "../../include/mmpc.h"
@@ -23,6 +24,7 @@
 #include "mmpc_mission.h"
 #include "mmpc_manipulate.h"
 #include "mmpc_round.h"
+#include "mmpc_suspend.h"
 #include "mmpc_guess.h"
 
 template <int KIND, int NC = 0, int MC = -1, int OPSC = -1, int LC = -1>
@@ -148,18 +150,35 @@ __global__ __launch_bounds__(MMPC_LPT_THREADS) void mmpc_lpt_order(int B, const 
     for (int i = t; i < B; i += MMPC_LPT_THREADS) { int v = iters[i]; v = v < 0 ? 0 : (v > 255 ? 255 : v); order[atomicAdd(&start[v], 1)] = i; }
 }
 
-// list of the instances a budgeted launch left suspended (any order), and their number
+// list of the instances a budgeted launch left suspended (any order), and their number (the per-entry logic: mmpc_suspend.h)
 __global__ __launch_bounds__(256) void mmpc_collect_suspended(int B, const int *__restrict__ status, int *__restrict__ list,
                                                              int *__restrict__ count) {
     const int b = blockIdx.x * 256 + threadIdx.x;
-    if (b < B && status[b] == MMPC_STATUS_SUSPENDED) list[atomicAdd(count, 1)] = b;
+    if (b < B) mmpc_suspend_collect(b, status, list, count);
 }
 
 // the same over a list of instances (list launches): only the listed ones can have been suspended by the launch before
 __global__ __launch_bounds__(256) void mmpc_collect_suspended_list(int B, const int *__restrict__ in_list, const int *__restrict__ in_count,
                                                                   const int *__restrict__ status, int *__restrict__ list, int *__restrict__ count) {
     const int w = blockIdx.x * 256 + threadIdx.x;
-    if (w < *in_count) { const int b = in_list[w]; if ((unsigned)b < (unsigned)B && status[b] == MMPC_STATUS_SUSPENDED) list[atomicAdd(count, 1)] = b; }
+    if (w < *in_count) mmpc_suspend_collect_listed(w, B, in_list, status, list, count);
+}
+
+// resume budget (mmpc_set_resume_budget): the handle's list compacted to the instances that are still suspended, into the handle's
+// other list buffer (a grid-stride loop: the length is on the device).  stamp != null: the first half of a merge
+__global__ __launch_bounds__(256) void mmpc_compact_suspended(int B, const int *__restrict__ in_list, const int *__restrict__ in_count,
+                                                             const int *__restrict__ status, int *__restrict__ list, int *__restrict__ count,
+                                                             int *__restrict__ stamp, int gen) {
+    const int n = *in_count < B ? *in_count : B;
+    for (int w = blockIdx.x * 256 + threadIdx.x; w < n; w += gridDim.x * 256) mmpc_suspend_compact(w, B, in_list, status, list, count, stamp, gen);
+}
+
+// ... and the second half: the rows of a list launch that were suspended, each appended once unless the list holds it already
+__global__ __launch_bounds__(256) void mmpc_append_suspended(int B, const int *__restrict__ in_list, const int *__restrict__ in_count,
+                                                            const int *__restrict__ status, int *__restrict__ list, int *__restrict__ count,
+                                                            int *__restrict__ stamp, int gen) {
+    const int w = blockIdx.x * 256 + threadIdx.x;
+    if (w < *in_count) mmpc_suspend_append(w, B, in_list, status, list, count, stamp, gen);
 }
 
 // A-priori difficulty of an instance, from its data alone: how close the reference path comes to (or how deep it cuts
@@ -312,6 +331,11 @@ struct mmpc_handle_s {
     int *d_list, *d_count;  // compacted list of the suspended instances of the last launch
     int resume_B;           // batch size of the budgeted launch whose suspended instances can still be continued (0: nothing to resume)
     int resume_fast;        // ... and the family that launch ran (1 specialised, 0 generic): its continuation runs the same one
+    // resume budget (mmpc_set_resume_budget): a continuation may suspend again, a budgeted list launch carries the suspended
+    int resume_budget;      // iterations a continuation may spend on an instance (0, the default: to the end)
+    int *d_list2, *d_count2;   // the other list buffer: a compaction or a merge writes it, then the two pairs change places
+    int *d_stamp;           // [max_batch] duplicate guard of a merge (mmpc_suspend.h): the number of the merge that took the row
+    int merge_gen;          // number of the last merge (the stamps start at 0, the numbers at 1)
     int no_lpt_env, force_generic_env;   // MMPC_NO_LPT / MMPC_FORCE_GENERIC, read once at create (diagnostics)
     int *d_warm;            // per instance: 1 once a CONVERGED solve has filled its u_latest / x_guess rows
     // device-side state and staging (capacity max_batch)
@@ -635,7 +659,7 @@ extern "C" int mmpc_destroy(mmpc_handle h) {
     if (!h) return MMPC_E_ARG;
     void *ptrs[] = {h->dp, h->d_x_init, h->d_traj, h->d_uref, h->d_obs, h->d_ulatest, h->d_xguess, h->d_X, h->d_U,
                     h->d_s, h->d_cost, h->d_err, h->d_u0, h->d_status, h->d_iters, h->d_order, h->d_warm, h->d_key, h->d_state,
-                    h->d_list, h->d_count, h->d_gscr, h->d_soc, h->d_ticket};
+                    h->d_list, h->d_count, h->d_gscr, h->d_soc, h->d_ticket, h->d_list2, h->d_count2, h->d_stamp};
     (void)hipSetDevice(h->cfg.device);
     if (h->ev_valid) (void)hipEventSynchronize(h->ev);
     if (h->ev) (void)hipEventDestroy(h->ev);
@@ -698,8 +722,10 @@ struct MmpcMode {
     const int *list, *count;
     int capacity;
     bool either_family;
+    bool to_end;   // a continuation that ignores the handle's resume budget (the one inside mmpc_solve_batch)
 };
-static const MmpcMode whole_batch = {MMPC_WHOLE_BATCH, nullptr, nullptr, 0, false}, continuation = {MMPC_CONTINUATION, nullptr, nullptr, 0, false};
+static const MmpcMode whole_batch = {MMPC_WHOLE_BATCH, nullptr, nullptr, 0, false, false}, continuation = {MMPC_CONTINUATION, nullptr, nullptr, 0, false, false},
+                      continuation_to_end = {MMPC_CONTINUATION, nullptr, nullptr, 0, false, true};
 
 static int launch(mmpc_handle h, int B, const MmpcBatch &a, hipStream_t st, const MmpcMode &mode) {
     const bool resume = mode.cover == MMPC_CONTINUATION;
@@ -714,6 +740,11 @@ static int launch(mmpc_handle h, int B, const MmpcBatch &a, hipStream_t st, cons
     if (resume && !((use_fast || gen_cont) && h->d_state && h->resume_B == B && h->resume_fast == (use_fast ? 1 : 0)))
         return fail(h, MMPC_E_UNSUPPORTED, "%s%s", h->gen_cont_fn ? "nothing to resume: the handle's last launch was not a budgeted launch of this batch size on the kernel family this one would run, or the weights / the terminal equality have changed since"
                                                                   : "nothing to resume: the handle's last launch was not a budgeted launch of this batch size on a specialised kernel");
+    // resume budget: a continuation gives every suspended instance at most that many iterations and stays valid; a budgeted list
+    // launch that could have been a continuation (same B, same family, nothing stale-making since) carries the suspended
+    const int rbudget = (resume && !mode.to_end) ? h->resume_budget : 0;
+    const bool carry = !resume && ulist && h->resume_budget > 0 && h->budget > 0 && (use_fast || gen_cont) && h->d_state && h->resume_B == B &&
+                       h->resume_fast == (use_fast ? 1 : 0);
     h->resume_B = 0;
     // launch order of the workgroups (results do not depend on it): the iteration counts of the handle's previous launch of
     // this batch size when there are any and the mode allows them, else the a-priori difficulty key of THIS batch's data
@@ -745,7 +776,7 @@ static int launch(mmpc_handle h, int B, const MmpcBatch &a, hipStream_t st, cons
         }
         hipLaunchKernelGGL(h->fast_fn[cont], dim3(resume ? (B < MMPC_RESUME_GRID ? B : MMPC_RESUME_GRID) : pgrid), dim3(MMPC_WAVE), 0, st,
                            h->dp, B, a.x_init, a.traj, a.uref, a.ulast, a.xguess, a.obs, a.X, a.U, a.s, a.status, a.iters, a.cost, a.err,
-                           resume ? h->d_list : order, resume ? 0 : h->budget, cont ? h->d_state : (double *)nullptr,
+                           resume ? h->d_list : order, resume ? rbudget : h->budget, cont ? h->d_state : (double *)nullptr,
                            cont ? h->state_doubles : 0, resume ? h->d_count : (const int *)nullptr,
                            resume ? (const int *)nullptr : ucount, h->d_gscr, h->d_soc, h->soc_doubles, h->d_tick,
                            h->scale_max_grad, h->d_scale_out, pers ? h->d_ticket : (int *)nullptr);
@@ -753,7 +784,7 @@ static int launch(mmpc_handle h, int B, const MmpcBatch &a, hipStream_t st, cons
         hipLaunchKernelGGL(h->gen_cont_fn, dim3(resume ? (B < MMPC_RESUME_GRID ? B : MMPC_RESUME_GRID) : grid), dim3(MMPC_WAVE), h->lds_bytes, st,
                            h->dp, B, a.x_init, a.traj, a.uref, a.ulast, a.xguess, a.obs, a.X, a.U, a.s, a.status, a.iters, a.cost, a.err,
                            resume ? h->d_list : order, h->d_soc, h->soc_doubles, h->d_tick, h->scale_max_grad, h->d_scale_out,
-                           resume ? (const int *)nullptr : ucount, resume ? 0 : h->budget, h->d_state, h->state_doubles,
+                           resume ? (const int *)nullptr : ucount, resume ? rbudget : h->budget, h->d_state, h->state_doubles,
                            resume ? h->d_count : (const int *)nullptr);
     } else
         hipLaunchKernelGGL(h->gen_fn, dim3(grid), dim3(MMPC_WAVE), h->gen_dyn_lds, st, h->dp, B, a.x_init, a.traj, a.uref, a.ulast,
@@ -762,9 +793,26 @@ static int launch(mmpc_handle h, int B, const MmpcBatch &a, hipStream_t st, cons
     HIPCHK(h, hipGetLastError());
     if ((use_fast || gen_cont) && h->budget > 0 && !resume) {
         // who is suspended: compacted list for mmpc_resume_batch_device
-        HIPCHK(h, hipMemsetAsync(h->d_count, 0, 4, st));
-        if (ulist) hipLaunchKernelGGL(mmpc_collect_suspended_list, dim3((mode.capacity + 255) / 256), dim3(256), 0, st, B, ulist, ucount, a.status, h->d_list, h->d_count);
-        else hipLaunchKernelGGL(mmpc_collect_suspended, dim3((B + 255) / 256), dim3(256), 0, st, B, a.status, h->d_list, h->d_count);
+        if (ulist && h->resume_budget > 0) {
+            // resume budget: the carried instances that are still suspended, then the listed ones, every row once (mmpc_suspend.h)
+            const int gen = h->merge_gen = h->merge_gen == 0x7fffffff ? 1 : h->merge_gen + 1;
+            HIPCHK(h, hipMemsetAsync(h->d_count2, 0, 4, st));
+            if (carry) hipLaunchKernelGGL(mmpc_compact_suspended, dim3((B + 255) / 256), dim3(256), 0, st, B, h->d_list, h->d_count, a.status, h->d_list2, h->d_count2, h->d_stamp, gen);
+            hipLaunchKernelGGL(mmpc_append_suspended, dim3((mode.capacity + 255) / 256), dim3(256), 0, st, B, ulist, ucount, a.status, h->d_list2, h->d_count2, h->d_stamp, gen);
+            std::swap(h->d_list, h->d_list2); std::swap(h->d_count, h->d_count2);
+        } else {
+            HIPCHK(h, hipMemsetAsync(h->d_count, 0, 4, st));
+            if (ulist) hipLaunchKernelGGL(mmpc_collect_suspended_list, dim3((mode.capacity + 255) / 256), dim3(256), 0, st, B, ulist, ucount, a.status, h->d_list, h->d_count);
+            else hipLaunchKernelGGL(mmpc_collect_suspended, dim3((B + 255) / 256), dim3(256), 0, st, B, a.status, h->d_list, h->d_count);
+        }
+        h->resume_B = B;
+        h->resume_fast = use_fast ? 1 : 0;
+    }
+    if (resume && rbudget > 0) {
+        // the continuation may have suspended its instances again: the list of those, for the next continuation (same B, same arguments)
+        HIPCHK(h, hipMemsetAsync(h->d_count2, 0, 4, st));
+        hipLaunchKernelGGL(mmpc_compact_suspended, dim3((B + 255) / 256), dim3(256), 0, st, B, h->d_list, h->d_count, a.status, h->d_list2, h->d_count2, (int *)nullptr, 0);
+        std::swap(h->d_list, h->d_list2); std::swap(h->d_count, h->d_count2);
         h->resume_B = B;
         h->resume_fast = use_fast ? 1 : 0;
     }
@@ -800,10 +848,25 @@ extern "C" int mmpc_set_iteration_budget(mmpc_handle h, int budget) {
         HIPCHK(h, hipMalloc(&h->d_list, B * 4));
         HIPCHK(h, hipMalloc(&h->d_count, 4));
         HIPCHK(h, hipMemset(h->d_count, 0, 4));
+        // (the second list buffer and the duplicate guard of mmpc_set_resume_budget)
+        HIPCHK(h, hipMalloc(&h->d_list2, B * 4));
+        HIPCHK(h, hipMalloc(&h->d_count2, 4));
+        HIPCHK(h, hipMemset(h->d_count2, 0, 4));
+        HIPCHK(h, hipMalloc(&h->d_stamp, B * 4));
+        HIPCHK(h, hipMemset(h->d_stamp, 0, B * 4));
     }
     if (h->ev_valid) HIPCHK(h, hipEventSynchronize(h->ev));
     h->budget = budget;
     h->resume_B = 0;
+    return MMPC_OK;
+}
+
+extern "C" int mmpc_set_resume_budget(mmpc_handle h, int budget) {
+    if (!h || budget < 0) return fail(h, MMPC_E_ARG, "mmpc_set_resume_budget: %s%s", "budget must be >= 0");
+    if (budget > 0 && !h->fast_fn[0] && !h->gen_cont_fn) return fail(h, MMPC_E_UNSUPPORTED, "mmpc_set_resume_budget: %s%s", "this (kind, N, M) runs the generic kernel, which has no continuation");
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    if (h->ev_valid) HIPCHK(h, hipEventSynchronize(h->ev));
+    h->resume_budget = budget;   // (a pending continuation stays valid: a solve is the same bits wherever it is cut)
     return MMPC_OK;
 }
 
@@ -934,7 +997,7 @@ extern "C" int mmpc_solve_batch(mmpc_handle h, int B, const double *x_init, cons
     int rc = launch(h, B, a, st, whole_batch);
     if (rc) return rc;
     if (h->budget > 0 && (h->fast_fn[0] || h->gen_cont_fn) && h->d_state) {   // the host-pointer call returns finished solves: continue the suspended ones at once
-        rc = launch(h, B, a, st, continuation);
+        rc = launch(h, B, a, st, continuation_to_end);   // (to the end whatever the resume budget is)
         if (rc && rc != MMPC_E_UNSUPPORTED) return rc;
     }
     // u_latest <- U*, x_guess <- X*  (:329-330), for the instances that converged
@@ -1311,6 +1374,44 @@ extern "C" int mmpc_mission_commit_device(mmpc_handle h, int B, int *d_hold, int
     if (h->ev_valid && st != h->last_stream) HIPCHK(h, hipStreamWaitEvent(st, h->ev, 0));
     HIPCHK(h, hipMemsetAsync(d_counters, 0, 4 * sizeof(int), st));
     hipLaunchKernelGGL(mmpc_commit_kernel, dim3(B), dim3(MMPC_WAVE), 0, st, h->cfg.N, B, d_hold, d_solve_phase, set, rejoin, d_U, d_status,
+                       d_iters, d_tick, d_phase, d_U_last, d_u0, d_iters_hist, d_status_hist, d_phase_hist, T, d_counters);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipEventRecord(h->ev, st));
+    h->ev_valid = 1; h->last_stream = st;
+    return MMPC_OK;
+}
+
+// the rejoin of a run with a resume budget (mmpc_set_resume_budget): a robot whose continuation was suspended again stays suspended
+__global__ __launch_bounds__(MMPC_WAVE) void mmpc_rejoin_kernel(
+    int N, int B, int *__restrict__ hold, int *__restrict__ solve_phase, int set, const double *__restrict__ U,
+    const int *__restrict__ status, const int *__restrict__ iters, const long long *__restrict__ tick, const int *__restrict__ phase,
+    double *__restrict__ U_last, double *__restrict__ u0, int *__restrict__ iters_hist, int *__restrict__ status_hist,
+    int *__restrict__ phase_hist, int T, int *__restrict__ counters) {
+    const int b = (int)blockIdx.x;
+    if (b >= B) return;
+    mmpc_rejoin_robot(N, b, hold, solve_phase, set, U, status, iters, tick, phase, U_last, u0, iters_hist, status_hist, phase_hist, T, counters);
+}
+
+extern "C" int mmpc_mission_rejoin_device(mmpc_handle h, int B, int *d_hold, int *d_solve_phase, int set, const double *d_U,
+                                          const int *d_status, const int *d_iters, const long long *d_tick, const int *d_phase,
+                                          double *d_U_last, double *d_u0, int *d_iters_hist, int *d_status_hist, int *d_phase_hist, int T,
+                                          int *d_counters, void *stream) {
+    if (!h) return MMPC_E_ARG;
+    if (h->cfg.kind != MMPC_KIND_WHOLEBODY)
+        return fail(h, MMPC_E_UNSUPPORTED, "mmpc_mission_rejoin_device: %s%s", "needs a whole-body handle (joint-space reference)");
+    if (B == 0) return MMPC_OK;
+    if (B < 1 || B > h->cfg.max_batch) return fail(h, MMPC_E_ARG, "mmpc_mission_rejoin_device: %s%s", "B must be in 0..max_batch");
+    if (!d_hold || !d_solve_phase || !d_U || !d_status || !d_iters || !d_tick || !d_phase || !d_U_last || !d_u0 || !d_iters_hist ||
+        !d_status_hist || !d_phase_hist || !d_counters)
+        return fail(h, MMPC_E_ARG, "mmpc_mission_rejoin_device: %s%s", "every array is required");
+    if (d_U_last == d_U) return fail(h, MMPC_E_ARG, "mmpc_mission_rejoin_device: %s%s", "d_U_last must not be d_U");
+    if (set < 0 || set > 15 || T < 1)
+        return fail(h, MMPC_E_ARG, "mmpc_mission_rejoin_device: %s%s", "set must be in 0..15, T at least 1");
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    hipStream_t st = (hipStream_t)stream;
+    if (h->ev_valid && st != h->last_stream) HIPCHK(h, hipStreamWaitEvent(st, h->ev, 0));
+    HIPCHK(h, hipMemsetAsync(d_counters, 0, 4 * sizeof(int), st));
+    hipLaunchKernelGGL(mmpc_rejoin_kernel, dim3(B), dim3(MMPC_WAVE), 0, st, h->cfg.N, B, d_hold, d_solve_phase, set, d_U, d_status,
                        d_iters, d_tick, d_phase, d_U_last, d_u0, d_iters_hist, d_status_hist, d_phase_hist, T, d_counters);
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipEventRecord(h->ev, st));

@@ -10,6 +10,8 @@
 // ticks retires: it gets the lock step's output-less call after the last tick (plant step, state machine) and is never touched
 // again.  A retiring call must enter no list and no count: it gets the workgroup's spare counters (zeroed here) and a list
 // capacity of 0, which mmpc_mission_one / mmpc_manipulate_one compare their list position with.
+// Under a resume budget (mmpc_set_resume_budget) a continuation may come back still suspended: the rejoin (mmpc_rejoin_robot) is the
+// rejoining commit except that such a robot stays suspended on its set and nothing of it is written.
 //
 // Same shared-source style as mmpc_mission.h (hipcc for gfx950, g++ -DMMPC_EMU -ffp-contract=off for the host: tests/round_emu).
 // No arithmetic of its own: every number is mmpc_mission_one's or mmpc_manipulate_one's, or a copy.
@@ -143,14 +145,22 @@ MMPC_DEV void mmpc_manipulate_round_robot(const MmpcParams &P, int b, int B, dou
     LANES_END
 }
 
-// robot b of the arrays of mmpc_mission_commit_device (include/mmpc.h)
-MMPC_DEV void mmpc_commit_robot(int N, int b, int *hold, int *solve_phase, int set, int rejoin, const double *U, const int *status,
-                                const int *iters, const long long *tick, const int *phase, double *U_last, double *u0, int *iters_hist,
-                                int *status_hist, int *phase_hist, int T, int *counters MMPC_EMU_ARG) {
+// the body of the commit and of the rejoin of robot b.  `again` (a constant of the caller): a robot whose continuation was suspended
+// again (status 3 under rejoin: mmpc_set_resume_budget) stays SUSPENDED + set and nothing of it is written - its hold word and its
+// solve phase included - but counters[1]; without it a status 3 under rejoin is committed
+MMPC_DEV void mmpc_commit_robot_body(int N, int b, int *hold, int *solve_phase, int set, int rejoin, bool again, const double *U,
+                                     const int *status, const int *iters, const long long *tick, const int *phase, double *U_last, double *u0,
+                                     int *iters_hist, int *status_hist, int *phase_hist, int T, int *counters MMPC_EMU_ARG) {
     const size_t r = (size_t)b, nu = (size_t)N * 5;
     const int h = hold[b];
     const bool mine = rejoin ? h == MMPC_HOLD_SUSPENDED + set : h == MMPC_HOLD_LISTED;
     const int st = mine ? status[b] : 0;
+    if (again && mine && st == 3) {
+        LANES_BEGIN
+        if (lane == 0) { mmpc_mission_take(counters + 1); mmpc_mission_take(counters + 3); }
+        LANES_END
+        return;
+    }
     const bool suspend = mine && st == 3 && !rejoin, commit = mine && !suspend;
     const int hn = suspend ? MMPC_HOLD_SUSPENDED + set : (commit ? MMPC_HOLD_READY : h);
     const long long t = tick[b];
@@ -183,4 +193,31 @@ MMPC_DEV void mmpc_commit_robot(int N, int b, int *hold, int *solve_phase, int s
             mmpc_mission_take(counters + 3);
     }
     LANES_END
+}
+
+// robot b of the arrays of mmpc_mission_commit_device (include/mmpc.h)
+MMPC_DEV void mmpc_commit_robot(int N, int b, int *hold, int *solve_phase, int set, int rejoin, const double *U, const int *status,
+                                const int *iters, const long long *tick, const int *phase, double *U_last, double *u0, int *iters_hist,
+                                int *status_hist, int *phase_hist, int T, int *counters MMPC_EMU_ARG) {
+#ifdef MMPC_EMU
+    mmpc_commit_robot_body(N, b, hold, solve_phase, set, rejoin, false, U, status, iters, tick, phase, U_last, u0, iters_hist, status_hist,
+                           phase_hist, T, counters, emu);
+#else
+    mmpc_commit_robot_body(N, b, hold, solve_phase, set, rejoin, false, U, status, iters, tick, phase, U_last, u0, iters_hist, status_hist,
+                           phase_hist, T, counters);
+#endif
+}
+
+// robot b of the arrays of mmpc_mission_rejoin_device (include/mmpc.h): the rejoin of the commit, except that a robot whose
+// continuation was suspended again stays suspended
+MMPC_DEV void mmpc_rejoin_robot(int N, int b, int *hold, int *solve_phase, int set, const double *U, const int *status, const int *iters,
+                                const long long *tick, const int *phase, double *U_last, double *u0, int *iters_hist, int *status_hist,
+                                int *phase_hist, int T, int *counters MMPC_EMU_ARG) {
+#ifdef MMPC_EMU
+    mmpc_commit_robot_body(N, b, hold, solve_phase, set, 1, true, U, status, iters, tick, phase, U_last, u0, iters_hist, status_hist,
+                           phase_hist, T, counters, emu);
+#else
+    mmpc_commit_robot_body(N, b, hold, solve_phase, set, 1, true, U, status, iters, tick, phase, U_last, u0, iters_hist, status_hist,
+                           phase_hist, T, counters);
+#endif
 }

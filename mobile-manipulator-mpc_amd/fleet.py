@@ -61,7 +61,13 @@ more ticks behind, while every other robot goes on.  The glue between two solves
 per robot (MMPC_HOLD_*), the mission and manipulate kernels under it (mmpc_mission_round_device, mmpc_manipulate_round_device), and a
 commit kernel that takes a round's solves into U_last and the per-tick histories (mmpc_mission_commit_device; csrc/mmpc_round.h).
 k groups of budgeted phase handles alternate; the per-robot results are those of run_mission without a budget, bit for bit.  The
-default stays budget=0.  Not built: mmpc_resume_batch_device runs to the end, so a 2 000-iteration solve still holds its handle set.
+default stays budget=0.  With resume_budget=0 (the default) mmpc_resume_batch_device runs to the end, so a 2 000-iteration solve holds its
+handle set until it is through and the main stream waits for it when the set's turn comes round again.
+
+run_mission(..., budget=b, sets=k, resume_budget=c): a continuation gives a solve at most c further iterations (mmpc_set_resume_budget) and
+parks it again; its robot stays held on its set (mmpc_mission_rejoin_device), the set's next list launch carries it in the handle's list
+of suspended instances and the next continuation goes on with it.  No round waits for more than c iterations of anybody; a carried solve
+advances c iterations per k rounds.  Same per-robot results, bit for bit.
 """
 import numpy as np
 
@@ -285,7 +291,7 @@ class DeviceFleet:
                 grp.append(c)
         return [[c._engine for c in grp[:4 if manipulate else 3]] for grp in self._mission_sets[:sets]]
 
-    def run_mission(self, T, streams=3, on_tick=None, manipulate=None, warm_start="reference", budget=0, sets=2, max_rounds=None, on_round=None):
+    def run_mission(self, T, streams=3, on_tick=None, manipulate=None, warm_start="reference", budget=0, sets=2, max_rounds=None, on_round=None, resume_budget=0):
         """T mission ticks.  streams=1: everything on the current stream; streams=3 (default: 0.5 % faster at B = 8192,
         profiles/fleet_mission.txt): the three list launches of a tick on three streams, forked after the mission kernel and joined
         before the next one; the results are bitwise the same.  Returns u0 (B,T,5), iters, status (B,T) - zero
@@ -324,7 +330,17 @@ class DeviceFleet:
         false.  shifted: set 0 is cold in round 0; every set gets mu_0 = 0.1 before its first warm round (a host wait per handle).
         Returned in addition: rounds, and suspended - the number of solves that used up their budget.  on_round(r, s): called after
         round r is queued, on the main stream, with the tensors counts (4,), counters (4,) = committed, suspended, failed, live of the
-        round's commit and, with manipulate, mcounts (2,); the next round rewrites them, so a caller that keeps them clones them."""
+        round's commit and, with manipulate, mcounts (2,); the next round rewrites them, so a caller that keeps them clones them.
+        resume_budget=0 (default): the above, unchanged.  resume_budget=c > 0 (needs budget > 0): the set's handles get
+        mmpc_set_resume_budget(c) for the run - every continuation gives a solve at most c further iterations and parks it again.  A
+        round on set s is then: wait for the set's continuations; mmpc_mission_rejoin_device in place of the rejoining commit - a robot
+        whose solve is still suspended stays held on set s, every other one rejoins; the round and guess kernels, which skip held
+        robots (so the inputs of a carried solve stay what it was launched with); the list launches, which keep the carried rows in
+        the handles' lists of suspended instances; their commit; the continuations, of carried and new rows alike.  Returned in
+        addition: resuspended - how often a continuation came back still suspended (the sum of counters[1] over the rejoin calls; a
+        solve of I > b iterations contributes ceil((I - b) / c) - 1).  A carried solve advances c iterations per `sets` rounds, so a
+        solve takes at most sets * ceil(max_iter / c) rounds beyond its first and the default max_rounds becomes
+        (sets + 2) T + 8 + T * sets * ceil(max_iter / c): a run whose solves all end cannot stop at the cap."""
         torch = self.torch
         if budget < 0:
             raise ValueError("budget must be >= 0, not %r" % (budget,))
@@ -333,6 +349,10 @@ class DeviceFleet:
         if budget > 0 and not self.generic_budget:
             raise ValueError("run_mission(budget=...) needs a fleet constructed with generic_budget=True: the approach, rotate and "
                              "manipulate handles run the generic kernel, which takes a budget only then")
+        if resume_budget < 0:
+            raise ValueError("resume_budget must be >= 0, not %r" % (resume_budget,))
+        if resume_budget > 0 and budget == 0:
+            raise ValueError("resume_budget=%r needs budget > 0: only a solve that was suspended is continued" % (resume_budget,))
         if budget == 0 and on_round is not None:
             raise ValueError("on_round belongs to a run under a budget; the lock step calls on_tick")
         if budget > 0 and on_tick is not None:
@@ -383,7 +403,7 @@ class DeviceFleet:
             mcnts = torch.zeros((T, 2), **i32)
             mkw = dict(pose=G["pose"], plan=G["plan"], lst=G["list"], counts=G["counts"], qgoal=G["qgoal"], ik_status=G["ik_status"])
         if budget > 0:
-            return self._mission_rounds(T, int(budget), sets, max_rounds, shifted, F, G if manip else None, mkw if manip else None, on_round)
+            return self._mission_rounds(T, int(budget), sets, max_rounds, shifted, F, G if manip else None, mkw if manip else None, on_round, int(resume_budget))
         for e in engs:
             e.set_iteration_budget(0); e.reset()
         x = self.x0.clone()
@@ -447,7 +467,7 @@ class DeviceFleet:
             res.update(mcounts=mcnts, qgoal=G["qgoal"].clone(), ik_status=G["ik_status"].clone(), plan=G["plan"].clone())
         return res
 
-    def _mission_rounds(self, T, budget, sets, max_rounds, shifted, F, G, mkw, on_round=None):
+    def _mission_rounds(self, T, budget, sets, max_rounds, shifted, F, G, mkw, on_round=None, resume_budget=0):
         """run_mission under a budget (its docstring): F, G the input buffers and the manipulate state run_mission has set up."""
         torch = self.torch
         B, N = self.B, self.N
@@ -469,6 +489,8 @@ class DeviceFleet:
         for grp in groups:
             for e in grp:
                 e.set_iteration_budget(budget); e.reset()
+                if resume_budget > 0:
+                    e.set_resume_budget(resume_budget)
         x = self.x0.clone()
         tick = self._clock0.zero_()[:B] if self.motion else torch.zeros(B, dtype=torch.int64, device=dev)
         phase, lists, counts = F["phase"].zero_(), F["lists"], F["counts"]
@@ -477,11 +499,14 @@ class DeviceFleet:
         ug, xg = (F["ug"], F["xg"]) if shifted else (None, None)
         hist = torch.zeros((B, T, 5), **f64)
         its, sts, phs = torch.zeros((B, T), **i32), torch.zeros((B, T), **i32), torch.full((B, T), -1, **i32)
-        nsusp = torch.zeros((), dtype=torch.int64, device=dev)
+        nsusp, nagain = torch.zeros((), dtype=torch.int64, device=dev), torch.zeros((), dtype=torch.int64, device=dev)
         main = torch.cuda.current_stream(dev)
         back = [None] * sets                 # per set: the events of its continuations in flight
         warm_set = [False] * sets
         cap = max_rounds if max_rounds is not None else (sets + 2) * T + 8
+        if max_rounds is None and resume_budget > 0:
+            # (a carried solve advances resume_budget iterations per `sets` rounds and ends at max_iter at the latest)
+            cap += T * sets * -(-max(int(e.max_iter) for e in groups[0]) // resume_budget)
         commit = lambda s, rejoin: glue.mission_commit(hold, sp, s, rejoin, out, tick, phase, U_last, hist, its, sts, phs, counters)
         r, live = 0, -1
         try:
@@ -493,7 +518,12 @@ class DeviceFleet:
                     for ev in back[s]:
                         main.wait_event(ev)
                     back[s] = None
-                    commit(s, 1)
+                    if resume_budget > 0:
+                        # (a robot whose solve is still suspended stays held on this set: the list launches below carry it)
+                        glue.mission_rejoin(hold, sp, s, out, tick, phase, U_last, hist, its, sts, phs, counters)
+                        nagain += counters[1]
+                    else:
+                        commit(s, 1)
                 glue.mission_round(x, tick, phase, lists, counts, U_last, hold, sp, T, glob=self.glob, x_in=F["x_in"], traj_ref=F["loc"], **tab)
                 if manip:
                     glue.manipulate_round(x, tick, phase, U_last=U_last, hold=hold, solve_phase=sp, tick_limit=T, x_in=F["x_in"],
@@ -532,6 +562,8 @@ class DeviceFleet:
                     ev.synchronize()
                 for e in groups[s]:
                     e.set_iteration_budget(0)
+                    if resume_budget > 0:
+                        e.set_resume_budget(0)
                     if warm_set[s]:
                         e.set_warm_start(None, 1.0)
         final = phase.clone()
@@ -539,7 +571,7 @@ class DeviceFleet:
         drive = torch.stack([(phs == p).sum(dim=0) for p in range(3)], dim=1).to(torch.int32)
         cnts = torch.cat([drive, (B - drive.sum(dim=1, keepdim=True)).to(torch.int32)], dim=1)
         res = dict(u0=hist, iters=its, status=sts, phase=phs, counts=cnts, x=x, final_phase=final,
-                   all_converged=(sts == 0).all() & torch.tensor(live == 0, device=dev), rounds=r, suspended=int(nsusp))
+                   all_converged=(sts == 0).all() & torch.tensor(live == 0, device=dev), rounds=r, suspended=int(nsusp), resuspended=int(nagain))
         if manip:
             res.update(mcounts=torch.stack([(phs == 4).sum(dim=0), (phs == 5).sum(dim=0)], dim=1).to(torch.int32), qgoal=G["qgoal"].clone(),
                        ik_status=G["ik_status"].clone(), plan=G["plan"].clone())

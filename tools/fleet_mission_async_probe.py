@@ -3,14 +3,17 @@ fleet of tools/fleet_mission_probe.py (B = 8192, N = 20, M = 3, tests/mission_em
 manipulate phase; writes profiles/fleet_mission_async.txt.
 
   python tools/fleet_mission_async_probe.py [--parent DIR] [--ticks T] [--robots B] [--rounds R] [--budgets 32,48,96] [--sets 2,3,4]
-                                            [--phases both|mission|manipulate] [--out FILE]
+                                            [--phases both|mission|manipulate] [--resume-budget 256,512,1024] [--out FILE]
       R rounds alternating the variants in rotating order, host clock around a run that ends in a synchronise, best and spread of each:
         1. run_mission on a default fleet, parent commit (--parent DIR: a checkout of the parent commit with its library built);
         2. the same on this build.  Condition: outputs bit for bit equal and this build's best within the parent's best plus this
            build's own spread;
         3. a generic_budget=True fleet, budget 0: the comparator of every run under a budget;
         4. that fleet with every budget x every number of handle sets: wall time, rounds, suspensions, outputs against variant 3,
-           and the time line of the last round by the round's lists (stream events through on_round).
+           and the time line of the last round by the round's lists (stream events through on_round);
+        5. --resume-budget: every budget x sets again with each resume budget c (run_mission(..., resume_budget=c): a continuation gives
+           a solve at most c further iterations and parks it again), with the count of re-suspensions; same comparison, same time line.
+           (profiles/fleet_mission_resuspend.txt: --budgets 96 --sets 3,4 --resume-budget 256,512,1024 --phases manipulate)
 """
 import argparse
 import importlib.util
@@ -44,6 +47,7 @@ def main():
     ap.add_argument("--parent"); ap.add_argument("--ticks", type=int, default=240); ap.add_argument("--robots", type=int, default=8192)
     ap.add_argument("--rounds", type=int, default=3); ap.add_argument("--budgets", default="32,48,96"); ap.add_argument("--sets", default="2,3,4")
     ap.add_argument("--phases", default="both", choices=("both", "mission", "manipulate"))
+    ap.add_argument("--resume-budget", default="", help="resume budgets of variant 5 (default: none)")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "fleet_mission_async.txt"))
     ap.add_argument("--commit", help="label of the code measured, for the report (default: git rev-parse HEAD)")
     args = ap.parse_args()
@@ -52,6 +56,7 @@ def main():
     import mission_emu_helper as H
     T, B = args.ticks, args.robots
     budgets, setss = [int(v) for v in args.budgets.split(",") if v], [int(v) for v in args.sets.split(",") if v]
+    resumes = [int(v) for v in args.resume_budget.split(",") if v]
     mm = mmpc_loader.load()
     F = H.mission_fleet(mm, B, N, 0.1)
     mk = lambda pkg, **kw: pkg.DeviceFleet(pkg, F["x0"], F["glob"], F["obs0"], F["vel"], N=N, **kw)
@@ -69,15 +74,15 @@ def main():
         keys = KEYS_MAN if manip else KEYS
         stamps = {}
 
-        def under_budget(b, k):
+        def under_budget(b, k, c=0):
             ev = []
 
             def on_round(r, s):
                 e = torch.cuda.Event(enable_timing=True); e.record()
                 ev.append((e, s["counts"].clone(), s["mcounts"].clone() if manip else None, s["counters"].clone()))
             e0 = torch.cuda.Event(enable_timing=True); e0.record()
-            res = generic.run_mission(T, budget=b, sets=k, on_round=on_round, **kw)
-            stamps[(b, k)] = (e0, ev)
+            res = generic.run_mission(T, budget=b, sets=k, on_round=on_round, **(dict(resume_budget=c) if c else {}), **kw)
+            stamps[(b, k, c)] = (e0, ev)
             return res
 
         variants = {}
@@ -88,6 +93,10 @@ def main():
         for b in budgets:
             for k in setss:
                 variants["4 budget %3d, sets %d" % (b, k)] = (lambda b=b, k=k: under_budget(b, k))
+        for b in budgets:
+            for k in setss:
+                for c in resumes:
+                    variants["5 budget %3d, sets %d, resume %4d" % (b, k, c)] = (lambda b=b, k=k, c=c: under_budget(b, k, c))
         times = {k: [] for k in variants}; last = {}
         full = T
         T = min(full, 4)                             # warm-up: handles, buffers, save areas, code objects - a few ticks are enough
@@ -115,11 +124,12 @@ def main():
         for name, v in times.items():
             r = last[name]
             extra = ""
-            if name.startswith("4"):
+            if name.startswith(("4", "5")):
                 same = all(bool(torch.equal(r[k], ref[k])) for k in keys)
-                extra = "  rounds %4d  suspended %7d  outputs bitwise those of variant 3: %s" % (r["rounds"], r["suspended"], same)
+                extra = "  rounds %4d  suspended %7d%s  outputs bitwise those of variant 3: %s" % (
+                    r["rounds"], r["suspended"], "  again %7d" % r["resuspended"] if name.startswith("5") else "", same)
                 rc |= 0 if same else 1
-            lines.append("  %-34s best %9.2f ms  spread %8.2f ms  (%s)  %8.0f solves/s%s" % (
+            lines.append("  %-38s best %9.2f ms  spread %8.2f ms  (%s)  %8.0f solves/s%s" % (
                 name, min(v), max(v) - min(v), " ".join("%.2f" % t for t in v), nsolve / (min(v) * 1e-3), extra))
         if pfleet is not None:
             rp, r2 = last["1 default fleet, parent commit"], last["2 default fleet, this build"]
@@ -131,7 +141,7 @@ def main():
             rc |= 0 if ok else 1
         lines.append("  time line of the last round of each run under a budget (per block of rounds: mean robots listed in move / approach / rotate"
                      "%s, mean suspended per round, mean live after the round, ms per round between stream events):" % (" / manipulate" if manip else ""))
-        for (b, k), (e0, ev) in stamps.items():
+        for (b, k, c), (e0, ev) in stamps.items():
             per = np.array([a.elapsed_time(c) for a, c in zip([e0] + [e[0] for e in ev[:-1]], [e[0] for e in ev])])
             cnt = torch.stack([e[1] for e in ev]).double().cpu().numpy()[:, :3]
             if manip:
@@ -139,7 +149,7 @@ def main():
             ctr = torch.stack([e[3] for e in ev]).double().cpu().numpy()
             R = len(ev)
             step = max(1, (R + 11) // 12)
-            lines.append("    budget %d, sets %d: %d rounds" % (b, k, R))
+            lines.append("    budget %d, sets %d%s: %d rounds" % (b, k, ", resume budget %d" % c if c else "", R))
             for lo in range(0, R, step):
                 hi = min(R, lo + step)
                 lines.append("      rounds %3d..%3d  %s  suspended %7.1f  live %6.0f  %8.3f ms" % (
